@@ -12,10 +12,21 @@ gradient buffer, for N>1 the RCCL SUM all-reduce of that buffer (loss pre-scaled
 MirroredStrategy do; the decoder / attention bucket is reduced under the encoder's backward), and the fused Keras-Nadam update
 (train.py:197,224) -- `value` INCLUDES the optimizer (`config.optimizer_in_step`); SURVEY 8d words the metric without it, so
 the optimizer-free rate of the same run is reported next to it (`without_optimizer`; `--no-optimizer` times only that).
-Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line; besides the contract fields it carries
-`roofline` (the (kernel, shape) with the largest total time in the step, timed alone with HIP events), `families` (every kernel
-family: ms/step, launches, executed TFLOP/s, algorithmic GB/s), `parity_mode` / `bf16_error` (the f32 mode that holds the 1e-3
-gate: its rate and error vs the CPU oracle; the timed bf16 mode's error vs that f32 mode) and `cpu_baseline`.
+Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line with the contract fields (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  A plain run does only what that headline needs: set-up, warm-up, the K
+timed steps, the result line.  `--full` adds every other measurement after the timed region: `without_optimizer`, `allreduce`
+(N>1), `roofline` (the (kernel, shape) with the largest total time in the step, timed alone with HIP events), `families` (every
+kernel family: ms/step, launches, executed TFLOP/s, algorithmic GB/s), `with_input_feed`, `parity_mode` / `bf16_error` (the f32
+mode that holds the 1e-3 gate: its rate and error vs the CPU oracle; the timed bf16 mode's error vs that f32 mode),
+`extra_configs` (BASELINE configs 4 and 5 in child runs) and `cpu_baseline`.
+`--dump-outputs DIR` writes DIR/<name>.npy (float32), after the timed region: the timed train step run once more from the
+state the run started in (seeded weights, fresh optimizer moments, the first step's Dropout / DropPath draws) -- its four loss
+terms and their sum, and a fixed seeded sample of the flat gradient buffer and of the flat weights after its update (--infer:
+a fixed sample of the last timed forward's logits).  Inputs and starting state are seeded, so two runs, or two builds, can be
+compared output for output: losses and gradients agree to rounding (bf16 rounding of an intermediate included); a weight whose
+gradient's sign is within that rounding takes Nadam's first update (~lr sign(g)) the other way, up to 2.11 lr apart.  (The last timed step itself cannot be compared: two runs'
+gradients differ by the rounding of f32 atomics, and the settle + warmup + steps Nadam updates of the same batch amplify that
+until the runs' gradients no longer agree.)
 """
 import argparse
 import json
@@ -37,6 +48,31 @@ MFMA_LOOP_RATE_TFLOPS = 1950.0        # what a bare 16x16x32 bf16 MFMA loop sust
 HBM_STREAM_CEILING_GBPS = 6750.0      # what a pure read stream reaches with every CU streaming (tools/probes/dma_lgkm_probe.hip): informational
 
 CFG256 = dict(input_size=(256, 256), window_size=8, embed_dim=96, depths=[2, 2, 2], num_heads=[3, 6, 12])
+DUMP_SAMPLE = 1 << 21                 # --dump-outputs: elements kept of each large output (8 MB as float32)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def sample_flat(t, seed):
+    """-> float32 host copy of the flat tensor t, or of a fixed seeded sample of DUMP_SAMPLE of its elements (sorted indices)."""
+    import numpy as np
+    import torch
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(seed).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy (float32 or float64), at most DUMP_MAX_BYTES in all."""
+    import numpy as np
+    nbytes = sum(a.nbytes for a in arrays.values())
+    if nbytes > DUMP_MAX_BYTES:
+        raise RuntimeError(f'bench.py: --dump-outputs would write {nbytes} bytes (limit {DUMP_MAX_BYTES})')
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirname, name + '.npy'), a)
 
 
 def synth_batch(B, seed, device, grid=256):
@@ -170,14 +206,17 @@ def bench_infer(args, model, x, world, rank, dist):
         out = step()
     barrier()
     dt_s = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'logits_sample': sample_flat(out, 0)})
     t = torch.tensor([dt_s], device=out.device)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt_s = float(t)
     single = None
+    extras = args.full and not args.no_kernel_timing
     # (not under --no-kernel-timing: that run executes exactly warmup + steps replays, which is what the rocprofv3 summaries divide by and what
     #  tools/timeline.py takes its step from)
-    if gf is not None and pipe and not args.no_kernel_timing:          # the same without the overlap: every step runs its own agent branch in front of the main graph
+    if gf is not None and pipe and extras:          # the same without the overlap: every step runs its own agent branch in front of the main graph
         barrier()
         t1 = time.perf_counter()
         for _ in range(args.steps):
@@ -185,7 +224,7 @@ def bench_infer(args, model, x, world, rank, dist):
         barrier()
         single = (time.perf_counter() - t1) / args.steps * 1e3
     roof = families = None
-    if not args.no_kernel_timing:        # every C-ABI launch of the forward timed alone (serial eager pass), as in the train leg
+    if extras:        # every C-ABI launch of the forward timed alone (serial eager pass), as in the train leg
         from strajnet_amd import prof as kprof
         model.serial = True
 
@@ -334,8 +373,8 @@ def run_extra_configs(steps=30, warmup=10):        # (10 + 3 steps of a fresh pr
     import subprocess
     res = {}
     for name, flags in (('infer', ['--infer']), ('cfg512', ['--cfg512'])):
-        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup), '--no-cpu-baseline',
-               '--no-extra-configs'] + flags
+        cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps', str(steps), '--warmup', str(warmup), '--full',
+               '--no-cpu-baseline', '--no-extra-configs'] + flags
         t0 = time.time()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
@@ -416,6 +455,11 @@ def main():
     ap.add_argument('--serial', action='store_true', help='no side streams: every kernel runs alone (the mode the roofline kernel timings are taken in)')
     ap.add_argument('--no-extra-configs', action='store_true', help='default N=1 run only: skip the child runs of BASELINE configs 4 (--infer) and 5 (--cfg512) that fill `extra_configs`, and the input-feed measurement')
     ap.add_argument('--gemm-trace', action='store_true', help='print per-shape GEMM launch times (HIP events) to stderr')
+    ap.add_argument('--full', action='store_true', help='after the timed region, every extra measurement and check as well (optimizer-free repeat, all-reduce '
+                    'timing, per-kernel roofline, input feed, f32 parity mode, CPU baseline, the child runs of BASELINE configs 4 and 5); '
+                    'the --no-* switches above still leave parts of it out.  Off: set-up, warm-up, the timed steps and the result line only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed region, run the timed step once more from the starting state and write what it computed '
+                    '(--infer: the last timed forward) as DIR/<name>.npy (float32)')
     args = ap.parse_args()
 
     import torch
@@ -474,6 +518,7 @@ def main():
     from strajnet_amd import dp
 
     finish_step_ref = [None]
+    terms_ref = [None]           # the last step's [observed_xe, occluded_xe, flow, flow_warp_xe] (--dump-outputs)
 
     def build_step(overlap):
         sync = dp.OverlappedGradSync(model) if overlap else None
@@ -498,6 +543,7 @@ def main():
             out = model(x['ogm'], x['map_img'], training=True, obs=x['obs'], occ=x['occ'], mapt=x['mapt'], flow=x['flow'])
             d = loss_fn(get_pred_waypoint_logits(out), tw, None)
             total = d.total                      # observed_xe + occluded_xe + flow + flow_warp_xe (train.py:221)
+            terms_ref[0] = d.packed
             if unit is not None:
                 total.backward(unit)
             else:
@@ -520,7 +566,7 @@ def main():
         eager_step = step
 
         def step_graph():
-            graphed(between=sync.tail if overlap else None)
+            terms_ref[0] = graphed(between=sync.tail if overlap else None)
             finish_step()
             return graphed.total             # the four terms' sum, written by the loss kernel inside the graph (no reduction launch between replays)
         if graphed is not None:
@@ -530,6 +576,21 @@ def main():
 
     overlap = world > 1 and not args.no_overlap
     step, eager_step, graphed, sync = build_step(overlap)
+
+    def train_state():
+        """The state a train step reads and updates: flat f32 weights, Nadam moments, the Dropout / DropPath stream position."""
+        return [model.flat_weights(), model.dropctx.state] + ([opt.m, opt.v] if opt is not None else [])
+
+    def snapshot():
+        return [t.clone() for t in train_state()], ((opt.t, opt.m_schedule) if opt is not None else None)
+
+    def restore(snap):
+        for dst, src in zip(train_state(), snap[0]):
+            dst.copy_(src)
+        if opt is not None:
+            opt.t, opt.m_schedule = snap[1]
+    # --dump-outputs: the state before the first step (seeded weights, fresh optimizer): the dumped step starts from it (see below)
+    start_state = snapshot() if args.dump_outputs else None
     probed = 0
     overlap_fallback_reason = None
     if overlap:          # the two-graph / two-bucket path has only ever run over gloo (no multi-GPU node so far): probe it once, and fall
@@ -582,10 +643,29 @@ def main():
         last = step()
     barrier()
     dt_s = time.perf_counter() - t0
+    loss_val = float(last.detach())
+    if args.dump_outputs:
+        # The timed step once more, from the state the run started in: the last timed step itself is not reproducible.  Its weights
+        # have taken settle + warmup + steps - 1 Nadam updates on the same batch, and the f32 atomics of the weight gradients make
+        # each update differ between runs by rounding, which those updates amplify (after 64 of them the gradients of two runs no
+        # longer agree at all).  One step from the seeded state agrees between runs to rounding.  The end state is put back after.
+        end_state = snapshot()
+        restore(start_state)
+        dumped = step()
+        barrier()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {'loss': dumped.detach().float().reshape(1).cpu().numpy(),
+                                             'loss_terms': terms_ref[0].detach().float().reshape(-1).cpu().numpy(),
+                                             'grads_sample': sample_flat(model.flat_grads(), 1),
+                                             'weights_sample': sample_flat(model.flat_weights(), 2)})
+        restore(end_state)
+        barrier()
+        del start_state, end_state
+    extras = args.full and not args.no_kernel_timing
     # SURVEY 8(d) words the metric as fwd + loss + bwd (+ all-reduce) WITHOUT the optimizer: the same K steps again with the
     # Nadam launch left out, reported next to the headline (which includes it)
     fwd_bwd_only = None
-    if opt is not None and not args.no_kernel_timing:
+    if opt is not None and extras:
         held, opt = opt, None
         step()
         barrier()
@@ -602,7 +682,7 @@ def main():
         fwd_bwd_only = {'value': round(B * world * args.steps / d1, 3), 'unit': 'scenes/s', 'ms_per_step': round(d1 / args.steps * 1e3, 3)}
     # the exchange step on its own (measured all-reduce time next to the ring model), outside the timed region
     allreduce = None
-    if world > 1:
+    if world > 1 and args.full:
         g = model.flat_grads()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         dist.all_reduce(g, op=dist.ReduceOp.SUM)
@@ -625,14 +705,15 @@ def main():
         dist_info = dp.OverlappedGradSync.info()
         dist_info['allreduce_overlapped_with_backward'] = bool(overlap)
         dist_info['overlap_fallback_reason'] = overlap_fallback_reason
-        chk = torch.ones(1, device=dev)
-        dist.all_reduce(chk)
-        dist_info['ranks_seen_by_allreduce'] = int(chk.item())       # every rank contributed 1: proof the collective spans N ranks
+        if args.full:
+            chk = torch.ones(1, device=dev)
+            dist.all_reduce(chk)
+            dist_info['ranks_seen_by_allreduce'] = int(chk.item())       # every rank contributed 1: proof the collective spans N ranks
     # per-kernel HIP-event timing of EVERY C-ABI launch (strajnet_amd/prof.py): the same launches, issued eagerly with events
     # recorded on the launch stream -- under graph replay individual launches cannot carry events
     prof_ser = prof_conc = None
     nprof = min(args.steps, 3)
-    if not args.no_kernel_timing:
+    if extras:
         from strajnet_amd import prof as kprof
         # (a) kernels ALONE: side streams off, so an event pair brackets exactly one kernel -- the roofline figures
         model.serial = True
@@ -654,23 +735,22 @@ def main():
         t = torch.tensor([dt_s], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt_s = float(t.item())
-    loss_val = float(last.detach())
-    if world > 1:
+    if world > 1 and args.full:
         lg = torch.tensor([loss_val], dtype=torch.float64, device=dev)
         dist.all_reduce(lg)                                          # the replica-scaled losses add up to the loss of the global batch
         dist_info['loss_global_batch'] = round(float(lg.item()), 4)
     feed = None
-    if rank == 0 and world == 1 and graphed is not None and not args.no_extra_configs and not args.no_kernel_timing:
+    if rank == 0 and world == 1 and graphed is not None and not args.no_extra_configs and extras:
         try:
             feed = input_feed(graphed, x, args.steps, finish_step_ref[0], dev)
         except Exception as e:
             feed = {'error': f'{type(e).__name__}: {e}'[:300]}
-    extras = {}
-    if rank == 0 and world == 1 and not args.no_kernel_timing and not args.cfg512 and dtype == torch.bfloat16:
+    parity = {}
+    if rank == 0 and world == 1 and extras and not args.cfg512 and dtype == torch.bfloat16:
         try:
-            extras = parity_extras(model, loss_fn, x, B, dev, not args.no_cpu_baseline)
+            parity = parity_extras(model, loss_fn, x, B, dev, not args.no_cpu_baseline)
         except Exception as e:          # reported extras, never the product path
-            extras = {'parity_mode': {'error': f'{type(e).__name__}: {e}'}}
+            parity = {'parity_mode': {'error': f'{type(e).__name__}: {e}'}}
 
     if rank == 0:
         scenes = B * world * args.steps
@@ -696,15 +776,15 @@ def main():
         if families:
             out['families'] = families
             out['kernel_ms'] = kern
-        out.update(extras)
+        out.update(parity)
         if feed is not None:
             out['with_input_feed'] = feed
-        if world == 1 and not args.cfg512 and not args.no_extra_configs and not args.no_kernel_timing and dtype == torch.bfloat16:
+        if world == 1 and not args.cfg512 and not args.no_extra_configs and extras and dtype == torch.bfloat16:
             del graphed
             torch.cuda.empty_cache()
             out['extra_configs'] = run_extra_configs()
         if 'cpu_baseline' not in out:
-            if not args.no_cpu_baseline and world == 1 and not args.cfg512:
+            if args.full and not args.no_cpu_baseline and world == 1 and not args.cfg512:
                 try:
                     out['cpu_baseline'] = cpu_baseline()[0]
                 except Exception as e:      # the CPU port is a reported extra, never the product path

@@ -660,7 +660,7 @@ def test_bench_two_ranks_on_one_gpu():
     for mode, extra in (('overlap', []), ('one_bucket', ['--no-overlap'])):
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                '--master-port', '29533', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '2',
-               '--no-kernel-timing', '--no-cpu-baseline'] + extra
+               '--full', '--no-kernel-timing', '--no-cpu-baseline'] + extra
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -676,6 +676,48 @@ def test_bench_two_ranks_on_one_gpu():
     assert abs(res['overlap']['loss'] - res['one_bucket']['loss']) < 2e-3 * abs(res['one_bucket']['loss'])
     lg = [res[m]['distributed']['loss_global_batch'] for m in ('overlap', 'one_bucket')]
     assert abs(lg[0] - lg[1]) < 2e-3 * abs(lg[1]) and lg[1] > res['one_bucket']['loss']
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """bench.py without --full: the headline only (no extra passes after the timed region), `steps` and `ms_per_step` as asked, and
+    --dump-outputs writing the losses and the gradient / weight samples of the timed step run from the seeded starting state, as
+    float32.  That step does not depend on how many steps the run timed, so two runs of different lengths dump the same outputs up to
+    the rounding of the f32 atomics in the weight gradients."""
+    import json
+    import subprocess
+    import sys
+    runs = []
+    for i, steps in enumerate((3, 5)):
+        d = tmp_path / f'run{i}'
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', str(steps), '--warmup', '1', '--settle', '0', '--batch', '2',
+               '--dump-outputs', str(d)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1, r.stdout[-2000:]
+        res = json.loads(lines[0])
+        assert res['steps'] == steps and res['warmup'] == 1 and res['ms_per_step'] > 0 and res['value'] > 0
+        assert res['unit'] == 'scenes/s' and res['higher_is_better'] and res['dtype'] == 'bf16'
+        assert res['roofline'] is None and res['without_optimizer'] is None and res['cpu_baseline'] is None
+        assert not {'families', 'parity_mode', 'with_input_feed', 'extra_configs'} & set(res)
+        arrs = {f.stem: np.load(f) for f in d.glob('*.npy')}
+        assert set(arrs) == {'loss', 'loss_terms', 'grads_sample', 'weights_sample'}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs['loss_terms'].shape == (4,) and abs(float(arrs['loss'][0]) - float(arrs['loss_terms'].sum())) <= 1e-4 * abs(float(arrs['loss'][0]))
+        assert arrs['grads_sample'].shape == arrs['weights_sample'].shape and float(np.abs(arrs['grads_sample']).max()) > 0
+        runs.append(arrs)
+    a, b = runs
+    # measured between pairs of runs: losses equal or 1e-7 apart; gradients within 1e-7 of their largest element, up to 1.5e-4 when an
+    # intermediate rounds to the other bf16 value (bf16 steps are 3.9e-3 relative)
+    np.testing.assert_allclose(a['loss_terms'], b['loss_terms'], rtol=1e-4)
+    np.testing.assert_allclose(a['loss'], b['loss'], rtol=1e-4)
+    gmax = float(np.abs(a['grads_sample']).max())
+    assert float(np.abs(a['grads_sample'].astype(np.float64) - b['grads_sample']).max()) <= 1e-3 * gmax
+    # Nadam's first update is ~1.056 lr sign(g) per element: where a gradient element's sign is within that rounding (measured at B = 8:
+    # under 0.01 % of the weights differ by more than 1e-6) the two runs' weights lie up to 2.11 lr apart; the others agree to rounding
+    dw = np.abs(a['weights_sample'].astype(np.float64) - b['weights_sample'])
+    assert float(dw.max()) <= 2.2e-4 and int((dw > 1e-6).sum()) <= 0.01 * dw.size
 
 
 def test_golden_train_step_gradients_f32():

@@ -1,9 +1,10 @@
 #!/bin/bash
-# copy an artifact set from gpurun_out/ (tools/final_artifacts.sh <tag>) into profiles/, merge its PMC traffic figures into profiles/roofline_traffic.json
+# copy an artifact set from $STJ_ARTIFACT_DIR (default artifacts/; tools/final_artifacts.sh <tag> writes it) into profiles/, merge its PMC traffic figures into profiles/roofline_traffic.json
 # (what bench.py quotes as roofline.traffic) and regenerate the kernel table.   usage: tools/adopt_artifacts.sh <tag>
 tag=$1
 cd "$(dirname "$0")/.."
-for f in gpurun_out/${tag}_*; do
+out=${STJ_ARTIFACT_DIR:-artifacts}        # where tools/final_artifacts.sh put the set
+for f in $out/${tag}_*; do
   case "$f" in *.err) continue;; esac
   cp "$f" profiles/
 done
