@@ -63,8 +63,6 @@ class GraphedTrainStep:
         if hasattr(self.loss_fn, 'prepare'):         # the ground-truth-only part of the loss: side stream, under the forward pass --
             if self._side is None:                   # issued from the model's mid-forward hook (behind the encoder's first stage: at the
                 self._side = ops.role_stream(torch.cuda.current_device(), 'loss_prep')     # head of the step its two launches delayed the first encoder kernel)
-                if hasattr(self.loss_fn, 'finalize_stream'):
-                    self.loss_fn.finalize_stream = self._side
 
             def prepare():
                 self._side.wait_stream(torch.cuda.current_stream())
@@ -80,8 +78,6 @@ class GraphedTrainStep:
         d = self.loss_fn(get_pred_waypoint_logits(out), tw, None)
         total = d.total                      # observed_xe + occluded_xe + flow + flow_warp_xe (train.py:221)
         total.backward(self._one)             # (an explicit tensor: backward()'s implicit ones_like is a fill launch on every replay)
-        if self._side is not None and ops.LOSS_FIN_SIDE:
-            main.wait_stream(self._side)      # the loss values' finalize launch (issued behind the loss pass on the side stream: off, see ops.LOSS_FIN_SIDE)
         self.total = total.detach()           # the sum the finalize kernel wrote (static across replays, like self.losses)
         return d.packed             # [observed_xe, occluded_xe, flow, flow_warp_xe], detached
 

@@ -91,7 +91,6 @@ class OGMFlow_loss:
         # forward pass (stj_loss_fwd_bwd) and backward hands it over when it is called with exactly that tensor -- any other
         # upstream gradient takes the general kernel.
         self.unit_grad = None
-        self.finalize_stream = None     # with unit_grad: a side stream for the launch that writes the loss VALUES (the caller joins it)
 
     def _flags(self):
         return (0 if self.no_use_warp else 1) | (2 if self.use_focal_loss else 0) | (4 if self.use_pred else 0)
@@ -149,7 +148,7 @@ class OGMFlow_loss:
             gate = torch.ones(8, dtype=torch.float32, device=logits.device)
         loss = ops.ogm_flow_loss(logits, gt_obs, gt_occ, gt_flow, origin, gate, self.ogm_weight, self.occ_weight,
                                  self.flow_origin_weight, self.replica, self._flags(),
-                                 coef=coef, unit=self.unit_grad if coef is not None else None, fin_stream=self.finalize_stream)
+                                 coef=coef, unit=self.unit_grad if coef is not None else None)
         d = LossDict({'observed_xe': loss[0], 'occluded_xe': loss[1], 'flow': loss[2],
                       'flow_warp_xe': loss[3] if not self.no_use_warp else 0.0})
         d.total, d.packed = loss[4], loss[5]       # the sum (differentiable) and the 4 values as one detached vector

@@ -234,10 +234,6 @@ class STrajNet:
         self.serial = False              # True: everything on the current stream (per-kernel timing, debugging)
         self.taps = None                 # a dict: call() stores detached float copies of the stage boundaries in it (tools/bf16_attribution.py)
         # fused Swin-block kernels (csrc/swin_fused.hip); STJ_FUSED_SWIN=0 selects the layer-by-layer path (the one the f32 mode's C = 384 stage takes)
-        # where the decoder's three skip GEMMs are issued on the side stream: 0 behind the encoder, 1 behind FG-MSA, 2 behind the cross-attention (round 6, the B = 32
-        # inference timeline has `fgattn_fwd` at 290 us beside them against 64 alone: 0 / 1 / 2 = 5803-5962 / 5854-5889 / 5741-5771 scenes/s, training 1407 / 1389-1418 / 1210:
-        # moving them moves the contention, profiles/r06_zk_skips_issue.txt)
-        self.skips_issue = 0
         self.fused_mlp = self.fused_attn = os.environ.get('STJ_FUSED_SWIN', '1') != '0'
         # C = 384 (the 16x16 stage: 2048 rows = 32 row blocks / 32 windows at B = 8) runs the SPLIT variants of the fused kernels --
         # (row block | window) x (slice of the hidden dimension | of the heads) workgroups + a finishing launch.  The f32 parity mode runs the
@@ -249,17 +245,11 @@ class STrajNet:
         # (the parity tests run both and compare)
         self.fused_xattn = True
         self.fused_stem = True         # PatchEmbed + the stem's sums / norms as one launch per raster (csrc/patch_embed.hip); False = im2col + dense + LayerNorm launches
-        self.agent_issue_mode = 2
         self.agent_override = None            # (key, mask) from agent_encode(): call() then skips the agent branch
         self.mid_forward_hook = None          # callable run once per forward pass behind the encoder's first stage (GraphedTrainStep: loss.prepare on its side stream)
         self.fused_fgattn = True       # FG-MSA attention core as one kernel per direction (8 x 8 / 16 x 16 maps; all three storage types)
-        self.kv_in_agent_branch = False # (measured neutral: 1333-1338 either way) the cross-attention's key / value projections of the agent encoding issued on the agent branch's stream
-        self._xattn_kv_pre = None
         self.fused_agent = True        # TrajEncoder of all agents as one kernel per direction (csrc/agent_fused.hip); False = the layer-by-layer chain
         self.fused_agent_int = True    # ... and the 64-agent interaction block (16-bit storage types)
-        # stage 0: the last block's weight gradients leave on the side stream under the first block's backward, so that the pass's final launch (122 us with
-        # nothing left to run beside it) halves.  Measured 1362 / 1365 / 1363 / 1365 with against 1366 / 1366 / 1368 / 1363 without: off
-        self.wg_mid_flush = False
         self.fused_fgoff = True        # FG-MSA's offset head (conv_offset -> tanh * range) as one kernel per direction (csrc/fgoff_fused.hip)
         self._agent_pack = None
         self._agent_pack_event = None
@@ -463,13 +453,9 @@ class STrajNet:
         if self.taps is not None:
             self.taps[name] = t.detach().float().clone()
 
-    def _basic_layer(self, x, pre, B, res, depth, heads, downsample, add=None, mid_flush=False):
+    def _basic_layer(self, x, pre, B, res, depth, heads, downsample, add=None):
         """BasicLayer.call (modules.py:351-364) -> (downsampled, pre-merge tokens)."""
         for i in range(depth):
-            if mid_flush and i == depth - 1:
-                # backward: the LAST block's weight gradients (and whatever else is queued) leave on the side stream while the blocks in front
-                # of it still run backward -- the final launch of the pass, which nothing can hide, is then half as long
-                x = ops.wgrad_queue_flush_point(x, side=True)
             x = self._swin_block(x, f'{pre}/blocks{i}', B, res, heads, 0 if i % 2 == 0 else 4)
             self._tap(f'{pre}/block{i}', x)
         if not downsample:
@@ -539,8 +525,7 @@ class STrajNet:
             return t.view(B, r, r, c)[:, q:q + r // 2, q:q + r // 2].reshape(B, (r // 2) ** 2, c)
         for i in range(3):
             r, c = self.stage_res[i], self.stage_dim[i]
-            x, res = self._basic_layer(x, f'layers{i}', B, r, depths[i], heads[i], i < 2, add=joined_flow_x if i == 0 else None,
-                                       mid_flush=self.wg_mid_flush and i == 0)
+            x, res = self._basic_layer(x, f'layers{i}', B, r, depths[i], heads[i], i < 2, add=joined_flow_x if i == 0 else None)
             if i < 2:       # in backward: stage i + 1 is through -> its weight gradients (and whatever else is queued) leave as one launch
                 x = ops.wgrad_queue_flush_point(x)
             if i == 0:
@@ -702,9 +687,10 @@ class STrajNet:
         o2 = self._ln(out[:, n_obs:].contiguous(), 'traj_net/occ_norm', 1e-3)
         return torch.cat([o1, o2], 1), cmi
 
-    def _resconv(self, skip, name):
+    def _resconv(self, skip, name, grad_is_pre):
         """ELU(Conv3D(8,1,1) SAME (tf.repeat(skip, 8))) collapsed exactly to 8 per-time 1x1 GEMMs with summed
-        time taps (modules.py:750-765): W_t = sum_{j=max(0,3-t)}^{min(7,10-t)} W[j]."""
+        time taps (modules.py:750-765): W_t = sum_{j=max(0,3-t)}^{min(7,10-t)} W[j].
+        grad_is_pre: the decoder level that adds this skip returns its gradient times ELU' (ops.upconv_add(skips_pre=True))."""
         pw, pb = self._p(name + '/kernel'), self._p(name + '/bias')
         Ci, Co = pw.shape[3], pw.shape[4]
         wz = torch.empty((8, Ci, Co), dtype=self.dtype, device=self.device)
@@ -713,9 +699,8 @@ class STrajNet:
 
         def fold():
             ops.call('stj_time_fold', ops._p(gwz), ops._p(pw.grad), Ci * Co, ops._st())
-        # (16-bit training: the decoder level that adds this skip returns its gradient times ELU' -- ops.upconv_add(skips_pre=True))
         return ops.linear_z(skip, pw.master, wz[0], Ci * Co, pb.master.detach(), 0, gwz[0], Ci * Co, pb.grad, 8,
-                            act=ACT_ELU, shared_x=True, fold=fold, grad_is_pre=ops.skips_pre_ok(self.dtype))    # [8, B*HW, Co]  (time-major)
+                            act=ACT_ELU, shared_x=True, fold=fold, grad_is_pre=grad_is_pre)    # [8, B*HW, Co]  (time-major)
 
     # ---- the 8 time-separated cross-attentions, batched over the waypoint axis z (trajNet.py:305-314) ----
     def _zp(self, suffix):
@@ -755,13 +740,12 @@ class STrajNet:
         if self.fused_xattn and A == 64 and HW % 64 == 0 and Cb == 384:
             # ONE kernel: q projection, masked softmax attention, out projection, LN, FFN, LN, + query (csrc/xattn_fused.hip);
             # only the projections of the 64 agent keys / values stay GEMMs (one grouped launch)
-            pre, self._xattn_kv_pre = self._xattn_kv_pre, None
-            k, v = pre if pre is not None else self._xattn_kv(key)
+            k, v = self._xattn_kv(key)
             ps = self._xattn_params()
             if self._xattn_pack_stale:
                 self._pack_xattn()
             return ops.xattn(query, k, v, tmask, self._xattn_pack, ps, zs, self._dctx,
-                             ('cross_attn_obs/mha/dropout', 'cross_attn_obs/dropout1', 'cross_attn_obs/dropout2'), defer_wg=pre is not None)
+                             ('cross_attn_obs/mha/dropout', 'cross_attn_obs/dropout1', 'cross_attn_obs/dropout2'))
         with ops.gemm_group():
             q = proj_in(query, 'mha/query_kernel', False)                    # [8, B*HW, 126]
             k = proj_in(key, 'mha/key_kernel', True)                         # [8, B*64, 126]
@@ -784,8 +768,9 @@ class STrajNet:
                            res=query.reshape(v1.shape))                             # + query (trajNet.py:317)
         return v1.view(Z, B, HW, Cb)
 
-    def _decoder(self, x, res_list, B, skips=None):
-        """Pyramid3DDecoder.call (modules.py:739-772): shallow_decode=1, flow_sep_decode, use_pyramid, rep_res."""
+    def _decoder(self, x, res_list, B, skips=None, skips_pre=False):
+        """Pyramid3DDecoder.call (modules.py:739-772): shallow_decode=1, flow_sep_decode, use_pyramid, rep_res.
+        skips_pre: ops.skips_pre_ok() as call() decided it for the skips' producers (_resconv's grad_is_pre)."""
         hb = self.hb
         flow_res, r0, r1 = res_list[0], res_list[1], res_list[2]
 
@@ -802,12 +787,12 @@ class STrajNet:
                 t.record_stream(main)
             s3, s2, sf = skips
         else:
-            s3, s2, sf = (self._resconv(r1, 'decoder/resconv_3'), self._resconv(r0, 'decoder/resconv_2'),
-                          self._resconv(flow_res, 'decoder/resconv_f'))
+            s3, s2, sf = (self._resconv(r1, 'decoder/resconv_3', skips_pre), self._resconv(r0, 'decoder/resconv_2', skips_pre),
+                          self._resconv(flow_res, 'decoder/resconv_f', skips_pre))
 
         def up_add(t, name, ra, rb=None):        # up-conv with the skip sum(s) in its epilogue (modules.py:750-765)
             return ops.upconv_add(t, self._p(name + '/kernel'), self._p(name + '/bias'), ra, rb, prep=self._upconv_prep.get(name),
-                                  skips_pre=ops.skips_pre_ok(self.dtype))
+                                  skips_pre=skips_pre)
         x = up_add(x, 'decoder/upconv_3_0', s3)                                      # [F,2hb,2hb,192]
         self._tap('decoder/level3', x)
         x, fx = up_add(x, 'decoder/upconv_2_0', s2, sf)                              # [F,4hb,4hb,128] x 2
@@ -916,16 +901,18 @@ class STrajNet:
         # independent of the raster encoder up to the cross-attention: it runs on a side stream, forked HERE.  Its launches are ISSUED
         # after the encoder's first stage though: a replayed hipGraph starts branches roughly in node-creation order, and issued first
         # the chain ran alone on an idle GPU for 0.5 ms before the first Swin kernel started (profiles/r02_c_timeline_concurrent.txt).
-        mode = self.agent_issue_mode if self._side is not None else -1       # (0: issued at the head of the step, 1: after the encoder -- both measured equal or worse)
-        main_pos = None
-        if mode in (3, 4, 5):           # on the MAIN stream: 4 = at the head of the step, 3 = behind the encoder, 5 = behind FG-MSA (in front of the cross-attention)
-            main_pos, mode = mode, -3
+        # (Issued at the head of the step / behind the whole encoder: 1331 / 1333 against 1333-1342 scenes/s; on the MAIN stream behind the
+        # encoder / at the head / behind FG-MSA: 1283-1287 / 1262 / 1303-1306)  Without a side stream it runs inline, here.
         agent = []
         if self.agent_override is not None:     # the caller ran agent_encode() itself (graph.GraphedForward: a graph of its own, a batch ahead)
             agent.extend(self.agent_override)
-            mode = -2
-
-        self._xattn_kv_pre = None
+        elif self._side is None:
+            agent.extend(self._traj_net(obs, occ))
+        branch = self._side is not None and self.agent_override is None
+        if branch:
+            main = torch.cuda.current_stream(self.device)
+            fork = torch.cuda.Event()
+            fork.record(main)
 
         def issue_agent():
             self._side.wait_event(fork)
@@ -933,40 +920,22 @@ class STrajNet:
                 self._side.wait_event(self._agent_pack_event)
             with torch.cuda.stream(self._side):
                 agent.extend(self._traj_net(obs, occ))
-                if self.kv_in_agent_branch and self.fused_xattn and agent[0].shape[1] == 64 and Cb == 384:
-                    # the 8 sets' key / value projections of the agent encoding belong to the cross-attention (trajNet.py:225) but depend on
-                    # the agent branch only: issued HERE, on its stream, their backward (two grouped launches, ~80 us in the step) runs beside
-                    # the FG-MSA backward instead of in front of it on the main stream -- and autograd, which runs the most recently
-                    # created nodes first, reaches FG-MSA's nodes before these
-                    self._xattn_kv_pre = self._xattn_kv(agent[0])
-        if mode >= 0:
-            main = torch.cuda.current_stream(self.device)
-            fork = torch.cuda.Event()
-            fork.record(main)
-        if mode == 0:
-            issue_agent()
-        elif mode == -1 or main_pos == 4:
-            agent.extend(self._traj_net(obs, occ))
         # Side work that is not needed before the cross-attention / the decoder / the loss is ISSUED behind the encoder's first stage
         # too: a replayed hipGraph starts its first ~20 nodes one after the other whatever their stream, so the seven packing /
         # folding launches and the caller's mid_forward_hook (graph.py: the ground-truth half of the loss) at the head of the step kept
         # the first encoder kernel waiting until 142 us (profiles/r04_b_timeline_concurrent.txt)
-        late = mode == 2 and self._side2 is not None
+        late = branch and self._side2 is not None
         if not late:
             issue_prep()
 
         def hook():
             if late:
                 issue_prep()
-            if mode == 2:
+            if branch:
                 issue_agent()
             if self.mid_forward_hook is not None:
                 self.mid_forward_hook()
         res_list = self._encoder(ogm, map_img, flow, hook=hook)
-        if mode == 1:
-            issue_agent()
-        if main_pos == 3:
-            agent.extend(self._traj_net(obs, occ))
         fold = self._fold_partials
         if self.cut_encoder and torch.is_grad_enabled():
             # data-parallel overlap: detach here; backward() then ends at these leaves (the tail bucket is complete and can be
@@ -975,20 +944,21 @@ class STrajNet:
             res_list = [t.detach().requires_grad_(True) for t in res_list]
             self._cut_leaf = res_list
             fold = lambda: self._fold_partials('tail')
+        # the skip contract of the decoder levels (_resconv's grad_is_pre = upconv_add's skips_pre), decided once for both sides
+        skips_pre = ops.skips_pre_ok(self.dtype)
         # the three time-kernel skips (Conv3D collapsed to per-waypoint 1x1 GEMMs) only need the encoder outputs: side stream,
-        # overlapping FG-MSA / the cross-attentions / the first up-convs; joined in the decoder where they are added
+        # overlapping FG-MSA / the cross-attentions / the first up-convs; joined in the decoder where they are added.  Issued right
+        # behind the encoder.  Round 6, behind the encoder / FG-MSA / the cross-attention: inference 5803-5962 / 5854-5889 / 5741-5771
+        # scenes/s, training 1407 / 1389-1418 / 1210 (the B = 32 inference timeline has `fgattn_fwd` at 290 us beside them against 64
+        # alone: moving them moves the contention; DESIGN.md 4o, the retired schedule switches)
         skips = None
-
-        def issue_skips():
-            main2 = torch.cuda.current_stream(self.device)
-            self._side2.wait_stream(main2)
+        if self._side2 is not None:
+            self._side2.wait_stream(torch.cuda.current_stream(self.device))
             for t in res_list[:3]:
                 t.record_stream(self._side2)
             with torch.cuda.stream(self._side2):
-                return (self._resconv(res_list[2], 'decoder/resconv_3'), self._resconv(res_list[1], 'decoder/resconv_2'),
-                        self._resconv(res_list[0], 'decoder/resconv_f'))
-        if self._side2 is not None and self.skips_issue == 0:
-            skips = issue_skips()
+                skips = (self._resconv(res_list[2], 'decoder/resconv_3', skips_pre), self._resconv(res_list[1], 'decoder/resconv_2', skips_pre),
+                         self._resconv(res_list[0], 'decoder/resconv_f', skips_pre))
         q = ops.wgrad_queue_flush_point(res_list[-1]).reshape(B, hb, hb, Cb)     # backward: FG-MSA / cross-attention / agent branch are through
         # waypoint-major [8,B,HW,Cb] (the reference's [B,8,...] transposed): every per-waypoint product downstream is then a
         # plain batched GEMM and the decoder frames are t-major; the output kernel undoes it when writing [B,H,W,32]
@@ -996,18 +966,11 @@ class STrajNet:
             q, query = self._fgmsa(q)                                              # modules.py:825-831
         else:
             query = q.reshape(1, B, hb * hb, Cb).expand(8, B, hb * hb, Cb).contiguous()   # modules.py:827
-        if self._side2 is not None and self.skips_issue == 1:       # behind FG-MSA: beside the cross-attention
-            skips = issue_skips()
-        if main_pos == 5:
-            agent.extend(self._traj_net(obs, occ))
         key, tmask = agent
-        if self._side is not None and mode >= 0:       # join the agent branch
+        if branch:       # join the agent branch
             main.wait_stream(self._side)
             key.record_stream(main)
             tmask.record_stream(main)
-            if self._xattn_kv_pre is not None:
-                for t in self._xattn_kv_pre:
-                    t.record_stream(main)
         self._tap('agent_key', key)
         self._tap('query', query)
         if self._prep_event is not None:                 # the packed cross-attention weights come from the side stream
@@ -1018,10 +981,8 @@ class STrajNet:
         # backward as well -- so that kernel has the GPU to itself -- measured 5 % SLOWER, 7.26 vs 6.88 ms: the 1.5 ms of half-GPU
         # weight-gradient launches then reach into the encoder's backward.)
         x = ops.wgrad_flush_point(x)
-        if self._side2 is not None and self.skips_issue == 2:       # behind the cross-attention: beside the first up-conv
-            skips = issue_skips()
         try:
-            out = self._decoder(x, res_list, B, skips)
+            out = self._decoder(x, res_list, B, skips, skips_pre)
         finally:
             ops.wgrad_defer_end()        # (also when the decoder raises: a stale "defer" flag would swallow the next stand-alone up-conv's weight gradient)
         self._tap('output', out)

@@ -24,6 +24,9 @@ def call(name, *args):
 
 
 GROUP_GEMMS = os.environ.get('STJ_GEMM_GROUP', '1') != '0'
+# STJ_NO_WS=1: the generic conv kernels instead of the MFMA / weight-stationary family (the paired output heads, the up-conv skip-sum
+# epilogue, the inference head), as in the library
+WS_KERNELS = os.environ.get('STJ_NO_WS') != '1'
 class _GroupState(threading.local):
     """per host thread (the forward thread and autograd's device threads each record into their own group, as the C ABI's contract says)"""
     def __init__(self):
@@ -229,9 +232,6 @@ def role_stream(device, role, priority=0):
 
 
 _WG = {}
-# bit 0: dense layers, bit 1: up-convs.  Measured (B=8): up-convs on the side stream +1 %; dense layers -9 % (their 768-block
-# split-K kernels crowd the data-gradient chain out of the CUs), so only the up-convs use it by default.
-_WG_MODE = 2
 
 
 _SERIAL = False
@@ -267,9 +267,11 @@ def wgrad_join_now(main):
         main.wait_stream(st['side'])
 
 
-def wgrad_stream(kind, *operands):
-    """Context manager: kernels launched inside run on the weight-gradient side stream of the operands' device."""
-    if _SERIAL or not (_WG_MODE & kind):
+def wgrad_stream(*operands):
+    """Context manager: kernels launched inside run on the weight-gradient side stream of the operands' device (the up-convs' weight
+    gradients only: measured at B=8, up-convs on the side stream +1 %, dense layers -9 % -- their 768-block split-K kernels crowd the
+    data-gradient chain out of the CUs)."""
+    if _SERIAL:
         return _NullCtx()
     dev = operands[0].device
     key = dev.index if dev.index is not None else torch.cuda.current_device()
@@ -310,10 +312,7 @@ class _JoinAfterBackward(torch.autograd.Function):
             # the weight-gradient side stream writes bias-gradient partials that `post` folds: it must be ordered before the fold
             # (its own join callback is queued later than this one and would run after it)
             key = g.device.index if g.device.index is not None else torch.cuda.current_device()
-            st = _WG.get(key)
             flush_upconv_wgrads()             # (leftovers: a flush point whose backward did not run)
-            with torch.cuda.stream(main), torch.no_grad():
-                run_pending_wg(g.device)      # (handed-over weight gradients nobody took)
             st = _WG.get(key)
             if st is not None and st['armed']:
                 main.wait_stream(st['side'])
@@ -477,25 +476,15 @@ def wgrad_queue_push(job, post=None, dev=None):
     _wq(dev)['jobs'].append((job, post, st, ev))
 
 
-def wgrad_queue_flush(dev=None, side=False):
+def wgrad_queue_flush(dev=None):
     """Launch everything queued (on `dev`; None: the current device), on the current stream.  (Round 5: the flush-point launches on the weight-gradient side stream instead,
     so that the next stage's backward need not wait for them, measured 1286-1291 scenes/s with all CUs as the launch's budget, 1270-1276
     with 128 workgroups, 1234-1246 with 96, against 1296-1305 on the main stream: the Swin backward kernels they would run beside fill
-    the CUs they are given, and the join before the optimizer waits for the slowed-down last flush.)
-    side=True: this one launch on the weight-gradient side stream (ordered behind the current stream, joined at the end of the pass)."""
+    the CUs they are given, and the join before the optimizer waits for the slowed-down last flush.)"""
     q = _wq(dev)
     items, q['jobs'] = q['jobs'], []
     if not items:
         return
-    if side and not _SERIAL:
-        keep = [t for job, _, _, _ in items for t in (job.x, job.dy) if isinstance(t, torch.Tensor)]
-        with wgrad_stream(1, *keep):
-            _wgrad_launch(items, dev)
-    else:
-        _wgrad_launch(items, dev)
-
-
-def _wgrad_launch(items, dev):
     cur = torch.cuda.current_stream(dev)
     last = {}
     for job, post, st, ev in items:
@@ -520,23 +509,21 @@ def wgrad_queue_end(dev=None):
 class _WgradQueueFlush(torch.autograd.Function):
     """Identity whose backward flushes the weight-gradient queue: everything downstream of it in the forward pass has been through."""
     @staticmethod
-    def forward(ctx, x, side):
-        ctx.side = side
+    def forward(ctx, x):
         return x.view_as(x)
 
     @staticmethod
     def backward(ctx, g):
-        wgrad_queue_flush(g.device, side=ctx.side)
-        return g, None
+        wgrad_queue_flush(g.device)
+        return g
 
 
-def wgrad_queue_flush_point(x, side=False):
-    if WGRAD_SK and WGRAD_SK_POINTS and x.requires_grad and torch.is_grad_enabled():
-        return _WgradQueueFlush.apply(x, side)
+def wgrad_queue_flush_point(x):
+    """Identity whose backward flushes the weight-gradient queue: a flush at every stage boundary, not only at the end of the pass (end
+    only: 1.5 % slower end to end)."""
+    if WGRAD_SK and x.requires_grad and torch.is_grad_enabled():
+        return _WgradQueueFlush.apply(x)
     return x
-
-
-WGRAD_SK_POINTS = True       # flush at the stage boundaries, not only at the end of the pass (end only: 1.5 % slower end to end)
 
 
 def _splitk(M_out, N_out, Kdim):
@@ -586,18 +573,16 @@ class _Linear(torch.autograd.Function):
         dx = None
         gw = ctx.gw if ctx.fold is None else zeros_f32((K, N), x2.device)
         # the two products are independent: one grouped launch for the small layers (big ones keep the row-streaming dgrad kernel)
-        with gemm_group(M < _GROUP_MAX_ROWS and not (_WG_MODE & 1)):
+        with gemm_group(M < _GROUP_MAX_ROWS):
             if ctx.needs_input_grad[0]:
                 dx = torch.empty_like(x2)
                 gemm(dpre, wc, dx, M, K, N, (0, 0, N, 1), (0, 0, 1, N), (0, 0, K), dt)        # dx = dpre W^T
                 dx = dx.view(ctx.xshape)
             fold = ctx.fold
-            with wgrad_stream(1, x2, dpre):
-                queued = gemm(x2, dpre, gw, K, N, M, (0, 0, 1, K), (0, 0, N, 1), (0, 0, N), dt, c_f32=1, accumulate=1,
-                              splitk=0, colsum=ctx.gb, post=(lambda: fold(gw)) if fold is not None else None)   # dW += x^T dpre ; db += 1^T dpre (fused)
+            queued = gemm(x2, dpre, gw, K, N, M, (0, 0, 1, K), (0, 0, N, 1), (0, 0, N), dt, c_f32=1, accumulate=1,
+                          splitk=0, colsum=ctx.gb, post=(lambda: fold(gw)) if fold is not None else None)   # dW += x^T dpre ; db += 1^T dpre (fused)
         if fold is not None and not queued:
-            with wgrad_stream(1, x2, dpre):
-                fold(gw)
+            fold(gw)
         dres = dy if ctx.has_res else None
         return dx, None, None, None, None, None, None, dres, None
 
@@ -607,25 +592,6 @@ def linear(x, pw, pb=None, act=ACT_NONE, res=None):
     N = pw.c.shape[-1]
     return _Linear.apply(x, pw.master, pw.c.view(-1, N), pw.grad.view(-1, N), pb.master if pb is not None else None,
                          pb.grad if pb is not None else None, act, res, None)
-
-
-# Weight-gradient launches handed from one backward node to another that runs on a different stream (the fused cross-attention's four
-# products -> the key / value projections' backward on the agent branch's stream): (closure, event behind the producer, operands).
-_PENDING_WG = {}
-
-
-def run_pending_wg(dev=None):
-    """Launch the handed-over weight gradients on the CURRENT stream of `dev` (ordered behind their producers)."""
-    idx = dev.index if dev is not None and dev.index is not None else torch.cuda.current_device()
-    items = _PENDING_WG.pop(idx, [])
-    if not items:
-        return
-    cur = torch.cuda.current_stream(dev)
-    for wg, ev, operands in items:
-        cur.wait_event(ev)
-        for t in operands:
-            t.record_stream(cur)
-        wg()
 
 
 class _HeadsIn(torch.autograd.Function):
@@ -652,9 +618,8 @@ class _HeadsIn(torch.autograd.Function):
         Z, R, H, I, hs, zstride, shared_x, xshape = ctx.dims
         dt = _dt(x)
         dy = dy.contiguous()
-        run_pending_wg(dy.device)
         dx = acc = None
-        with gemm_group(R < _GROUP_MAX_ROWS and not (_WG_MODE & 1)):          # input and weight gradient: independent products
+        with gemm_group(R < _GROUP_MAX_ROWS):          # input and weight gradient: independent products
             if ctx.needs_input_grad[0]:
                 # dx[z] = sum_h dy[z][:, h-slice] W[z,h]^T : the head sum is the K-segment loop of ONE GEMM per z
                 dx = torch.empty(xshape, dtype=x.dtype, device=x.device)
@@ -665,9 +630,9 @@ class _HeadsIn(torch.autograd.Function):
                 else:
                     gemm(dy, ctx.w0, dx, R, I, hs, (R * H * hs, 0, H * hs, 1), (zstride, 0, 1, hs), (R * I, 0, I), dt, nb=(Z, 1),
                          kseg=(H, hs, I * hs))
-            with wgrad_stream(1, x, dy):      # dW[z,h] += x_z^T dy_z[:, h-slice], straight into the flat gradient buffer
-                gemm(x, dy, ctx.gw0, I, hs, R, (0 if shared_x else R * I, 0, 1, I), (R * H * hs, hs, H * hs, 1), (zstride, I * hs, hs),
-                     dt, nb=(Z, H), c_f32=1, accumulate=1, splitk=0)
+            # dW[z,h] += x_z^T dy_z[:, h-slice], straight into the flat gradient buffer
+            gemm(x, dy, ctx.gw0, I, hs, R, (0 if shared_x else R * I, 0, 1, I), (R * H * hs, hs, H * hs, 1), (zstride, I * hs, hs),
+                 dt, nb=(Z, H), c_f32=1, accumulate=1, splitk=0)
         if acc is not None:
             call('stj_cast', _p(acc), 0, _p(dx), dt, R * I, _st())
         return (dx,) + (None,) * 6
@@ -727,7 +692,7 @@ class _LinearZ(torch.autograd.Function):
         else:
             dpre = dy
         dx = acc = None
-        with gemm_group(R < _GROUP_MAX_ROWS and not (_WG_MODE & 1)):          # input and weight gradient: independent products
+        with gemm_group(R < _GROUP_MAX_ROWS):          # input and weight gradient: independent products
             if ctx.needs_input_grad[0]:
                 if shared_x and R >= 4096:
                     # dx[r,:] = sum_z dpre[z,r,:] W_z^T : ONE GEMM whose contraction runs over the Z segments (z, n) -- no atomics
@@ -740,14 +705,12 @@ class _LinearZ(torch.autograd.Function):
                     dx = torch.empty_like(x)
                     gemm(dpre, ctx.w0, dx, R, K, N, (0, R * N, N, 1), (0, wstride, 1, N), (0, R * K, K), dt, nb=(1, Z))
             # dW_z += x_z^T dpre_z ; db_z += column sums (fused)
-            with wgrad_stream(1, x, dpre):
-                queued = gemm(x, dpre, ctx.gw0, K, N, R, (0, 0 if shared_x else R * K, 1, K), (0, R * N, N, 1), (0, gwstride, N), dt,
-                              nb=(1, Z), c_f32=1, accumulate=1, splitk=0, colsum=ctx.gb0, sBias=(0, bstride), post=ctx.fold)
+            queued = gemm(x, dpre, ctx.gw0, K, N, R, (0, 0 if shared_x else R * K, 1, K), (0, R * N, N, 1), (0, gwstride, N), dt,
+                          nb=(1, Z), c_f32=1, accumulate=1, splitk=0, colsum=ctx.gb0, sBias=(0, bstride), post=ctx.fold)
         if acc is not None:
             dx = acc.to(x.dtype).view(xshape)
         if ctx.fold is not None and not queued:
-            with wgrad_stream(1, x, dpre):
-                ctx.fold()
+            ctx.fold()
         return (dx,) + (None,) * 13
 
 
@@ -931,7 +894,7 @@ class _SwinMlp(torch.autograd.Function):
         call('stj_swin_mlp_bwd', _p(x), _p(dy), _p(pg.master), _p(pb.master), _p(pw1.c), _p(pb1.master), _p(pw2.c), _p(dx), _p(h),
              _p(dpre), _p(ln), _p(dys), _p(dg), _p(db), nparts, pstride, M, C, eps, _p(state), site, float(p_drop), rps, dt, _p(_swin_ws(x, M, C)), _st())
         g2 = dys if dys is not None else dy.view(M, C)
-        with wgrad_stream(1, ln, dpre, h, g2), gemm_group(M < _GROUP_MAX_ROWS):
+        with gemm_group(M < _GROUP_MAX_ROWS):
             gemm(ln, dpre, pw1.grad, C, 4 * C, M, (0, 0, 1, C), (0, 0, 4 * C, 1), (0, 0, 4 * C), dt, c_f32=1, accumulate=1,
                  splitk=0, colsum=pb1.grad)                               # dW1 += LN(x)^T dpre ; db1 += 1^T dpre
             gemm(h, g2, pw2.grad, 4 * C, C, M, (0, 0, 1, 4 * C), (0, 0, C, 1), (0, 0, C), dt, c_f32=1, accumulate=1,
@@ -1039,7 +1002,7 @@ class _SwinAttnHalf(torch.autograd.Function):
             gemm(dq2, pwq.c, dln, M, C, 3 * C, (0, 0, 3 * C, 1), (0, 0, 1, 3 * C), (0, 0, C), dt)         # dln = dqkv Wqkv^T
             call('stj_layernorm_bwd', _p(dln), _p(x), _p(pg.master), _p(mean), _p(rstd), _p(dx), _p(dg), _p(db), M, C, 0, 0, 0, 1, 0,
                  _p(dy), np_, ps_, dt, _st())                                                             # + the shortcut gradient
-        with wgrad_stream(1, a2, dys2, ln2, dq2), gemm_group(M < _GROUP_MAX_ROWS):
+        with gemm_group(M < _GROUP_MAX_ROWS):
             gemm(a2, dys2, pwp.grad, C, C, M, (0, 0, 1, C), (0, 0, C, 1), (0, 0, C), dt, c_f32=1, accumulate=1, splitk=0,
                  colsum=pbp.grad)                                                                         # dWp += a^T dys ; dbp
             gemm(ln2, dq2, pwq.grad, C, 3 * C, M, (0, 0, 1, C), (0, 0, 3 * C, 1), (0, 0, 3 * C), dt, c_f32=1, accumulate=1,
@@ -1339,16 +1302,13 @@ def xattn_pack(ps, zstride, Z, dtype, out=None):
     return out
 
 
-XATTN_WG_KIND = 1      # (2 = on the up-conv weight-gradient side stream: 1250 vs 1335 scenes/s, round 5 -- one more fork off the main chain and the graph executor serialises the deferred up-conv weight gradients with it)
-
-
 class _XAttn(torch.autograd.Function):
     """y = LN2(FFN(LN1(MHA(query, k, v)))) + query for Z weight sets (trajNet.py:224-234,305-317).  query [Z,B,HW,384]; k, v [Z,B*64,126]
     (projected keys / values: their projections stay autograd nodes of their own); ps: Params of set 0 (set z lies zstride elements
     further in the flat buffers).  Backward = ONE kernel + the dk / dv tile reduction + one grouped launch of the four weight-gradient
     GEMMs, on operands the backward kernel writes once."""
     @staticmethod
-    def forward(ctx, query, k, v, trig, kvalid, pack, ps, zstride, drop, defer_wg=False):
+    def forward(ctx, query, k, v, trig, kvalid, pack, ps, zstride, drop):
         _req_cuda(query, k, v)
         query, k, v = query.contiguous(), k.contiguous(), v.contiguous()
         Z, B, HW, Cb = query.shape
@@ -1365,7 +1325,7 @@ class _XAttn(torch.autograd.Function):
         call('stj_xattn_fwd', _p(query), _p(k), _p(v), _p(kvalid), _p(pack), _p(ps['bo'].master), _p(ps['g1'].master), _p(ps['be1'].master),
              _p(ps['b1'].master), _p(ps['b2'].master), _p(ps['g2'].master), _p(ps['be2'].master), zstride, _p(y), _p(sq), _p(so), _p(sv1),
              _p(su2), Z, B, HW, _p(state), sites[0], sites[1], sites[2], float(p_drop), dt, _st())
-        ctx.ps, ctx.zstride, ctx.drop, ctx.pack, ctx.defer_wg = ps, zstride, drop, pack, defer_wg
+        ctx.ps, ctx.zstride, ctx.drop, ctx.pack = ps, zstride, drop, pack
         ctx.save_for_backward(query, k, v, kvalid, sq, so, sv1, su2)
         return y
 
@@ -1395,10 +1355,10 @@ class _XAttn(torch.autograd.Function):
              _p(ps['b1'].master), _p(ps['g2'].master), zs, _p(sq), _p(sv1), _p(su2), _p(dquery), _p(dk), _p(dv), _p(dkp), _p(dvp), _p(hd),
              _p(dpre), _p(du2), _p(n1), _p(dv1), _p(dq), _p(ps['g1'].grad), _p(ps['be1'].grad), _p(ps['bo'].grad), _p(ps['g2'].grad),
              _p(ps['be2'].grad), Z, B, HW, _p(state), sites[0], sites[1], sites[2], float(p_drop), dt, _st())
-        # the four weight gradients of the Z sets, straight into the flat gradient buffer: one grouped launch -- here, or (defer_wg) handed to
-        # the key / value projections' backward, which runs on the agent branch's stream: nobody on the main chain waits for them
-        def wg():
-          with wgrad_stream(XATTN_WG_KIND, hd, dpre, du2, n1, dv1, dq, so, query), gemm_group():
+        # the four weight gradients of the Z sets, straight into the flat gradient buffer: one grouped launch on the current stream
+        # (on the up-conv weight-gradient side stream: 1250 vs 1335 scenes/s, round 5 -- one more fork off the main chain, and the graph
+        # executor serialises the deferred up-conv weight gradients with it)
+        with gemm_group():
             gemm(hd, du2, ps['w2'].grad, 512, 384, R, (0, R * 512, 1, 512), (0, R * 384, 384, 1), (0, zs, 384), dt, nb=(1, Z), c_f32=1,
                  accumulate=1, splitk=0, colsum=ps['b2'].grad, sBias=(0, zs))                      # dW2 += hd^T du2 ; db2
             gemm(n1, dpre, ps['w1'].grad, 128, 512, R, (0, R * 128, 1, 128), (0, R * 512, 512, 1), (0, zs, 512), dt, nb=(1, Z), c_f32=1,
@@ -1407,16 +1367,10 @@ class _XAttn(torch.autograd.Function):
                  c_f32=1, accumulate=1, splitk=0)                                                  # dWo[z,h] += O_h^T dv1
             gemm(query, dq, ps['wq'].grad, 384, 42, R, (R * 384, 0, 1, 384), (R * 144, 48, 144, 1), (zs, 384 * 42, 42), dt, nb=(Z, 3),
                  c_f32=1, accumulate=1, splitk=0)                                                  # dWq[z,h] += query^T dq_h
-        if ctx.defer_wg:
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(dev))
-            _PENDING_WG.setdefault(dev.index, []).append((wg, ev, (hd, dpre, du2, n1, dv1, dq, so, query)))
-        else:
-            wg()
-        return dquery, dk, dv, None, None, None, None, None, None, None
+        return dquery, dk, dv, None, None, None, None, None, None
 
 
-def xattn(query, k, v, kvalid, pack, ps, zstride, dctx=None, names=None, p_drop=0.1, defer_wg=False):
+def xattn(query, k, v, kvalid, pack, ps, zstride, dctx=None, names=None, p_drop=0.1):
     """Fused Cross_AttentionT x Z.  ps: dict of set-0 Params {wq, wo, bo, g1, be1, w1, b1, w2, b2, g2, be2}; dctx / names: the three
     dropout sites of a training step (attention coefficients, after FFN1, after FFN2), registered with the unfused draw shapes."""
     Z, B, HW, _ = query.shape
@@ -1425,7 +1379,7 @@ def xattn(query, k, v, kvalid, pack, ps, zstride, dctx=None, names=None, p_drop=
         sites = (dctx.site(names[0], (Z, B, 3, HW, 64), p_drop), dctx.site(names[1], (Z, B * HW, 512), p_drop),
                  dctx.site(names[2], (Z, B * HW, 384), p_drop))
         drop = (float(p_drop), dctx.snap, sites)
-    return _XAttn.apply(query, k, v, _trig(ps['wq'].master), kvalid, pack, ps, zstride, drop, defer_wg and not _SERIAL)
+    return _XAttn.apply(query, k, v, _trig(ps['wq'].master), kvalid, pack, ps, zstride, drop)
 
 
 def _xattn_cost(kind):
@@ -1862,7 +1816,7 @@ class _AgentEnc(torch.autograd.Function):
         # the three weight gradients on what the kernel wrote (queued on the grouped stream-K launch inside a model's backward pass)
         zq = ws['e_wk'].grad.data_ptr() - ws['e_wq'].grad.data_ptr()
         assert ws['e_wv'].grad.data_ptr() - ws['e_wk'].grad.data_ptr() == zq and zq % 4 == 0
-        with gemm_group(not (_WG_MODE & 1)), wgrad_stream(1, s_cat, dpre_s, s_att, dout, s_nodes, dqkv):
+        with gemm_group():
             gemm(s_cat, dpre_s, ws['e_ws'].grad, 384, 384, B * A, (0, 0, 1, 384), (0, 0, 384, 1), (0, 0, 384), dt, c_f32=1, accumulate=1,
                  splitk=0, colsum=ws['e_bs'].grad)
             gemm(s_att, dout, ws['e_wo'].grad.view(256, 320), 256, 320, rows, (0, 0, 1, 256), (0, 0, 320, 1), (0, 0, 320), dt, c_f32=1,
@@ -1965,8 +1919,7 @@ class _AgentBranch(torch.autograd.Function):
         H, hs = 6, C // 6
         zq = ws['e_wk'].grad.data_ptr() - ws['e_wq'].grad.data_ptr()
         assert ws['e_wv'].grad.data_ptr() - ws['e_wk'].grad.data_ptr() == zq and zq % 4 == 0
-        keep = list(si.values()) + list(dY.values()) + list(se.values()) + [dpre_s, dout, dqkv]
-        with gemm_group(not (_WG_MODE & 1)), wgrad_stream(1, *keep):
+        with gemm_group():
             for x, dy, w in ((si['s_qin'], dY['dq'], 'i_wq'), (si['s_concat'], dY['dk'], 'i_wk'), (si['s_concat'], dY['dv'], 'i_wv')):
                 gemm(x, dy, ws[w].grad, C, hs, R, (0, 0, 1, C), (0, hs, C, 1), (0, C * hs, hs), dt, nb=(1, H), c_f32=1, accumulate=1, splitk=0)   # dW[h] += x^T dy[:, h]
             gemm(si['s_att'], dY['dv1'], ws['i_wo'].grad.view(C, C), C, C, R, (0, 0, 1, C), (0, 0, C, 1), (0, 0, C), dt, c_f32=1, accumulate=1,
@@ -2102,9 +2055,8 @@ class _PatchEmbed(torch.autograd.Function):
                 dy = _ln_bwd_plain(dy, x2, mean2, rstd2, pg2, pb2, M, N)         # gradient of x2 = LN(pre) + add
             dadd = dy.view(ctx.add_shape) if ctx.has_add else None
             dpre = _ln_bwd_plain(dy, pre, mean, rstd, pg, pb, M, N)
-        with wgrad_stream(1, cols, dpre):
-            gemm(cols, dpre, gw, K, N, M, (0, 0, 1, K), (0, 0, N, 1), (0, 0, N), _dt(cols), c_f32=1, accumulate=1, splitk=0,
-                 colsum=pbias.grad)                                                # dW += cols^T dpre ; db += 1^T dpre
+        gemm(cols, dpre, gw, K, N, M, (0, 0, 1, K), (0, 0, N, 1), (0, 0, N), _dt(cols), c_f32=1, accumulate=1, splitk=0,
+             colsum=pbias.grad)                                                    # dW += cols^T dpre ; db += 1^T dpre
         return (None,) * 7 + (dadd,) + (None,) * 4
 
 
@@ -2204,10 +2156,10 @@ def _upconv_backward_tail(ctx, x, dpre, wd, need_dx):
         call('stj_upconv_fold', _p(dweff), _p(pw.grad), Cin, Cout, _st())
         if own:
             pb.grad.add_(dbp.view(nparts, Cout).sum(0))
-    if ctx.defer and not _SERIAL and (_WG_MODE & 2):
+    if ctx.defer and not _SERIAL:
         _UPWG['items'].append((wg, x, dpre))             # launched by flush_upconv_wgrads() (the model's flush point)
     else:
-        with wgrad_stream(2, x, dpre):
+        with wgrad_stream(x, dpre):
             wg()
     return dx
 
@@ -2221,23 +2173,18 @@ def _upconv_backward_tail(ctx, x, dpre, wd, need_dx):
 _UPWG = {'on': False, 'items': []}
 
 
-# Issue order of the deferred launches.  'bwd' = the order backward produced them (full-resolution layers first, the two wide layers
-# 192 -> 128 / 384 -> 192 last: those are 1024-workgroup non-persistent launches and land on Swin stage 2's backward); 'wide' = widest
-# Cin first, so that they run beside the thin FG-MSA / agent chain and only the budgeted persistent launches reach into the encoder.
-UPWG_ORDER = 'wide'     # round 6, alternating same-box runs: bwd 1350 / 1363 / 1349, wide 1372 / 1365 / 1359, rev 1340 / 1351 / 1353 scenes/s
-
-
 # (Releasing the OLDEST deferred launches -- the 256 x 256 level's -- already at the two-skip level's junction, beside the junction and the two wide input-gradient
 #  kernels that run alone there: 1 / 2 / 4 launches early 1352 / 1362 / 1355 scenes/s against 1380 with all of them deferred, profiles/r06_t_ab_upwg_early.txt.)
 def flush_upconv_wgrads():
     items, _UPWG['items'] = _UPWG['items'], []
     if not items:
         return
-    if UPWG_ORDER == 'wide':
-        items = sorted(items, key=lambda it: -it[1].shape[-1])        # (stable: equal widths keep their backward order)
-    elif UPWG_ORDER == 'rev':
-        items = items[::-1]
-    with wgrad_stream(2, *[t for it in items for t in it[1:]]):
+    # Widest Cin first: they then run beside the thin FG-MSA / agent chain, and only the budgeted persistent launches reach into the
+    # encoder.  Round 6, alternating same-box runs: widest first 1372 / 1365 / 1359 scenes/s; in backward order (full-resolution layers
+    # first, the two wide layers 192 -> 128 / 384 -> 192 last: 1024-workgroup non-persistent launches that land on Swin stage 2's
+    # backward) 1350 / 1363 / 1349; reversed 1340 / 1351 / 1353.
+    items = sorted(items, key=lambda it: -it[1].shape[-1])        # (stable: equal widths keep their backward order)
+    with wgrad_stream(*[t for it in items for t in it[1:]]):
         for wg, _, _ in items:
             wg()
 
@@ -2251,15 +2198,14 @@ class _WgradFlushPoint(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         flush_upconv_wgrads()
-        if WGRAD_SK_POINTS:
-            wgrad_queue_flush(g.device)     # the decoder's dense weight gradients (the three time-kernel skips)
+        wgrad_queue_flush(g.device)     # the decoder's dense weight gradients (the three time-kernel skips)
         return g
 
 
 def wgrad_flush_point(x):
     """Mark x as the input of the region whose up-conv weight gradients are deferred (no-op without autograd).
     The region ends at wgrad_defer_end()."""
-    _UPWG['on'] = DEFER_UPWG and x.requires_grad and torch.is_grad_enabled()
+    _UPWG['on'] = x.requires_grad and torch.is_grad_enabled()
     _UPWG['items'] = []
     return _WgradFlushPoint.apply(x) if _UPWG['on'] else x
 
@@ -2267,9 +2213,6 @@ def wgrad_flush_point(x):
 def wgrad_defer_end():
     """End of the forward region opened by wgrad_flush_point(): up-convs applied from here on do not defer."""
     _UPWG['on'] = False
-
-
-DEFER_UPWG = True
 
 
 class _UpConv(torch.autograd.Function):
@@ -2353,10 +2296,6 @@ class _UpConvAdd(torch.autograd.Function):
 # B=32 fp16 forward 1.4 % faster.
 
 
-SKIP_BWD_FUSED = True      # (False: the level's backward junction as an elementwise add + the ELU' pass; the f32 mode always)
-SKIP_JUNCTION = True       # the junction also applies the SKIPS' ELU' (stj_skip_junction_bwd); False: one stj_unary_bwd per skip, as up to round 5
-
-
 class _UpConvSkips(torch.autograd.Function):
     """y1 = ELU(upconv(x)) + r1 [, y2 = y1 + r2] (a decoder level with its skips, modules.py:750-765) with the forward as the launches that
     measure fastest in training (the up-conv, then the elementwise adds) and the backward's junction as ONE launch:
@@ -2409,7 +2348,7 @@ FUSED_SKIP_TRAIN = False       # (tests flip it: the fused form's backward, stj_
 def skips_pre_ok(dtype):
     """Will upconv_add(skips_pre=True) take the gradients' ELU' products on itself (so the skips' producers are to be called with
     grad_is_pre=True)?  The training form of the 16-bit modes; decided HERE for both sides of the contract."""
-    return SKIP_BWD_FUSED and SKIP_JUNCTION and not FUSED_SKIP_TRAIN and dtype != torch.float32 and torch.is_grad_enabled()
+    return not FUSED_SKIP_TRAIN and dtype != torch.float32 and torch.is_grad_enabled()
 
 
 def upconv_add(x, pw, pb, r1, r2=None, prep=None, skips_pre=False):
@@ -2422,9 +2361,9 @@ def upconv_add(x, pw, pb, r1, r2=None, prep=None, skips_pre=False):
         if not skips_pre_ok(x.dtype):
             raise RuntimeError('upconv_add(skips_pre=True) outside skips_pre_ok(): the skips would lose their ELU\' factor')
         return _UpConvSkips.apply(x, r1.view(oshape), None if r2 is None else r2.view(oshape), pw.master, pb.master, pw, pb, prep, True)
-    if (FUSED_SKIP_TRAIN or not torch.is_grad_enabled()) and x.dtype != torch.float32 and Cin > 128 and Cin % 32 == 0 and Cout % 32 == 0 and os.environ.get('STJ_NO_WS') != '1':
+    if (FUSED_SKIP_TRAIN or not torch.is_grad_enabled()) and x.dtype != torch.float32 and Cin > 128 and Cin % 32 == 0 and Cout % 32 == 0 and WS_KERNELS:
         return _UpConvAdd.apply(x, r1.view(oshape), None if r2 is None else r2.view(oshape), pw.master, pb.master, pw, pb, prep)
-    if SKIP_BWD_FUSED and r2 is not None and x.dtype != torch.float32 and torch.is_grad_enabled():
+    if r2 is not None and x.dtype != torch.float32 and torch.is_grad_enabled():
         return _UpConvSkips.apply(x, r1.view(oshape), r2.view(oshape), pw.master, pb.master, pw, pb, prep, False)
     y = upconv(x, pw, pb, prep=prep)
     y = y + r1.view(y.shape)
@@ -2454,9 +2393,6 @@ def _outconv_workspace(device):
     return _workspace(device, 'stj_outconv_bwd_workspace_bytes')
 
 
-PAIR_OUTCONV = os.environ.get('STJ_NO_WS') != '1'     # (the paired kernel belongs to the MFMA / weight-stationary family)
-
-
 class _OutConvPair(torch.autograd.Function):
     """Two 3x3 C->2 heads written straight into the [B,H,W,32] f32 model output (channel 4t+{0,1} and 4t+{2,3})."""
     @staticmethod
@@ -2471,7 +2407,7 @@ class _OutConvPair(torch.autograd.Function):
         inner = Tn
         if t_major:            # frames ordered f = t*B + b: the kernel's (f / inner, f % inner) split then yields (t, b)
             ybs, yts, inner = 4, H * W * 4 * Tn, B
-        if PAIR_OUTCONV and dt != 0 and C == 48 and Tn == 8 and H % 16 == 0 and W % 16 == 0:
+        if WS_KERNELS and dt != 0 and C == 48 and Tn == 8 and H % 16 == 0 and W % 16 == 0:
             call('stj_outconv_pair_fwd', _p(xo), _p(xf), _p(p1w.master), _p(p2w.master), _p(p1b.master), _p(p2b.master), _p(out),
                  B, Tn, H, W, C, int(bool(t_major)), dt, _st())
         else:
@@ -2496,13 +2432,15 @@ class _OutConvPair(torch.autograd.Function):
         #  1285 scenes/s, and -9 % on the weight-gradient side stream -- the fork at the head of backward reorders the graph's branches)
         call('stj_outconv_bwd', _p(xo), _p(p1w.master), vp(dout.data_ptr()), _p(dxo), _p(p1w.grad), _p(p1b.grad), F_, H, W, C, Tn,
              ybs, yts, yps, ctx.elu_in, _p(ws), ws.numel(), dt, _st())
-        side = ctx.side if (OUTCONV_BWD_TWO_STREAMS and not _SERIAL) else None
+        side = None if _SERIAL else ctx.side
         if side is not None:
             # the second head on the stream its branch's backward continues on (the model's second side stream): the first branch's input
-            # gradient then starts behind ITS head instead of behind both
+            # gradient then starts behind ITS head instead of behind both (round 6, alternating same-box runs: 1383 / 1383 / 1382 / 1385
+            # against 1376 / 1376 / 1379 / 1365 scenes/s on one stream).  The slot-1 workspace first: its one-time zero fill on main is
+            # then ordered in front of the side-stream launch.
+            ws2 = _workspace(xo.device, 'stj_outconv_bwd_workspace_bytes', 1)
             main = torch.cuda.current_stream(xo.device)
             side.wait_stream(main)
-            ws2 = _workspace(xo.device, 'stj_outconv_bwd_workspace_bytes', 1)
             with torch.cuda.stream(side):
                 call('stj_outconv_bwd', _p(xf), _p(p2w.master), vp(dout.data_ptr() + 8), _p(dxf), _p(p2w.grad), _p(p2b.grad), F_, H, W, C, Tn,
                      ybs, yts, yps, ctx.elu_in, _p(ws2), ws2.numel(), dt, _st())
@@ -2518,7 +2456,7 @@ def upconv_head_ok(Hi, Wi, pw, dtype, Tn):
     """True when the inference form of the last level (kernel pw) applies to an input [F,Hi,Wi,96]: no autograd, 16-bit, 96 -> 48, whole
     8 x 16 tiles, 8 waypoints."""
     return (not torch.is_grad_enabled() and dtype != torch.float32 and tuple(pw.master.shape[2:]) == (96, 48) and Hi % 8 == 0 and Wi % 16 == 0
-            and Tn == 8 and os.environ.get('STJ_NO_WS') != '1')
+            and Tn == 8 and WS_KERNELS)
 
 
 HEAD_CZ = 20       # channels of the projected tensor z: 9 taps x 2 outputs + 2 zero channels (csrc/conv_ws.hip HEAD_CZ)
@@ -2543,9 +2481,6 @@ def heads_gather(zo, zf, p1b, p2b, B, Tn, t_major=False):
     return out
 
 
-OUTCONV_BWD_TWO_STREAMS = True     # round 6, alternating same-box runs: 1383 / 1383 / 1382 / 1385 against 1376 / 1376 / 1379 / 1365 scenes/s on one stream
-
-
 def outconv_pair(xo, xf, p1w, p1b, p2w, p2b, B, Tn, t_major=False, x_is_elu_out=False, side=None):
     """side: the stream the second branch (xf) was computed on, when the caller runs the two branches on two streams."""
     return _OutConvPair.apply(xo, xf, p1w.master, p1b.master, p2w.master, p2b.master, p1w, p1b, p2w, p2b, B, Tn, t_major, x_is_elu_out, side)
@@ -2558,7 +2493,7 @@ class _OgmFlowLoss(torch.autograd.Function):
     """-> (observed_xe, occluded_xe, flow, flow_warp_xe, total): five 0-dim tensors.  `total` (their sum, train.py:221) is an output
     of its own so that a step which only differentiates the sum runs no select / add / zeros glue around the two loss kernels."""
     @staticmethod
-    def forward(ctx, logits, gt_obs, gt_occ, gt_flow, origin, gate, ogm_w, occ_w, fow, replica, flags, coef_pre=None, unit=None, fin_stream=None):
+    def forward(ctx, logits, gt_obs, gt_occ, gt_flow, origin, gate, ogm_w, occ_w, fow, replica, flags, coef_pre=None, unit=None):
         _req_cuda(logits)
         logits = logits.contiguous().float()
         B, H, W, _ = logits.shape
@@ -2572,20 +2507,10 @@ class _OgmFlowLoss(torch.autograd.Function):
             sums = zeros_f32(128 * 40, dev)
             dlogits = torch.empty_like(logits)
             w = (B, H, W, float(ogm_w), float(occ_w), float(fow), float(replica), int(flags))
-            ctx.fin_stream = fin_stream if (LOSS_FIN_SIDE and not _SERIAL) else None
-            if ctx.fin_stream is None:
-                call('stj_loss_fwd_bwd', _p(logits), _p(gt_obs), _p(gt_occ), _p(gt_flow), _p(origin), _p(gate), _p(coef_pre), _p(sums), _p(loss),
-                     _p(coef), _p(dlogits), *w, _st())
-            else:
-                # the loss VALUES are read by nobody on the backward path: their 1-workgroup finalize launch goes behind the pass on the
-                # caller's side stream (the caller joins it: GraphedTrainStep, after backward) instead of in front of the first backward kernel
-                call('stj_loss_fwd_bwd', _p(logits), _p(gt_obs), _p(gt_occ), _p(gt_flow), _p(origin), _p(gate), _p(coef_pre), _p(sums), None,
-                     None, _p(dlogits), *w, _st())
-                ctx.fin_stream.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(ctx.fin_stream):
-                    call('stj_loss_finalize', _p(sums), _p(gate), _p(loss), _p(coef), *w, _st())
-                for t in (sums, gate, loss, coef):
-                    t.record_stream(ctx.fin_stream)
+            # (the loss values' 1-workgroup finalize launch on the caller's side stream instead, behind the pass: 1355 / 1360 / 1357
+            #  against 1379 / 1380 / 1380 scenes/s here -- a fork / join more in the replayed graph, profiles/r06_u_loss_one_pass.txt)
+            call('stj_loss_fwd_bwd', _p(logits), _p(gt_obs), _p(gt_occ), _p(gt_flow), _p(origin), _p(gate), _p(coef_pre), _p(sums), _p(loss),
+                 _p(coef), _p(dlogits), *w, _st())
             ctx.unit_grad, ctx.dlogits = unit, dlogits
         else:
             sums = zeros_f32(32 * 40, dev)       # 32 copies of the 40 accumulators (stj_loss_fwd)
@@ -2604,16 +2529,14 @@ class _OgmFlowLoss(torch.autograd.Function):
         B, H, W, flags = ctx.geo
         parts = (g0, g1, g2, g3)
         if all(g is None for g in parts) and gt is None:
-            return (None,) * 14
+            return (None,) * 13
         if ctx.unit_grad is not None and ctx.dlogits is not None and all(g is None for g in parts) and gt.data_ptr() == ctx.unit_grad.data_ptr():
             LOSS_FUSED_STATS['hits'] += 1          # the announced unit gradient: d/dlogits was written by the forward pass
             dl, ctx.dlogits = ctx.dlogits, None
-            return (dl,) + (None,) * 13
+            return (dl,) + (None,) * 12
         if ctx.unit_grad is not None:              # (also a second backward through a retained graph: the stored gradient was handed over once)
             LOSS_FUSED_STATS['misses'] += 1        # some other upstream gradient: the general kernel (the forward's d/dlogits is dropped)
             ctx.dlogits = None
-            if ctx.fin_stream is not None:         # (its coefficients come from the finalize launch)
-                torch.cuda.current_stream(logits.device).wait_stream(ctx.fin_stream)
         if all(g is None for g in parts):
             up = gt.float().contiguous()             # one value for the four terms (flag bit 3): no expand / copy launch
             flags |= 8
@@ -2625,11 +2548,10 @@ class _OgmFlowLoss(torch.autograd.Function):
         dlogits = torch.empty_like(logits)
         call('stj_loss_bwd', _p(logits), _p(gt_obs), _p(gt_occ), _p(gt_flow), _p(origin), _p(coef), _p(up), _p(dlogits), B, H, W,
              flags, _st())
-        return (dlogits,) + (None,) * 13
+        return (dlogits,) + (None,) * 12
 
 
 LOSS_FUSED_BWD = True      # OGMFlow_loss with an announced unit gradient (loss_fn.unit_grad, set by GraphedTrainStep) + prepare(): stj_loss_fwd_bwd
-LOSS_FIN_SIDE = False      # ... with the launch that writes the loss VALUES on the caller's side stream (loss_fn.finalize_stream) instead of in front of the first backward kernel: 1355 / 1360 / 1357 against 1379 / 1380 / 1380 scenes/s on the main stream (a fork / join more in the replayed graph), profiles/r06_u_loss_one_pass.txt
 LOSS_FUSED_STATS = {'hits': 0, 'misses': 0}
 
 
@@ -2669,7 +2591,6 @@ def auc_gate(gt_obs, gt_occ, gt_flow, origin, return_auc=False):
     return (gate, auc) if return_auc else gate
 
 
-def ogm_flow_loss(logits, gt_obs, gt_occ, gt_flow, origin, gate, ogm_w, occ_w, fow, replica, use_warp, coef=None, unit=None, fin_stream=None):
-    """coef + unit: the prepared backward coefficients (loss_coef) and the unit gradient tensor `total` will be differentiated with;
-    fin_stream: a side stream for the launch that turns the sums into the loss values (the caller waits for it before reading them)."""
-    return _OgmFlowLoss.apply(logits, gt_obs, gt_occ, gt_flow, origin, gate, ogm_w, occ_w, fow, replica, use_warp, coef, unit, fin_stream)
+def ogm_flow_loss(logits, gt_obs, gt_occ, gt_flow, origin, gate, ogm_w, occ_w, fow, replica, use_warp, coef=None, unit=None):
+    """coef + unit: the prepared backward coefficients (loss_coef) and the unit gradient tensor `total` will be differentiated with."""
+    return _OgmFlowLoss.apply(logits, gt_obs, gt_occ, gt_flow, origin, gate, ogm_w, occ_w, fow, replica, use_warp, coef, unit)

@@ -807,7 +807,7 @@ def test_loss_and_gate():
     assert rel_err(lt.grad2, lt.grad) < 1e-6
 
 
-def test_loss_forward_writes_the_gradient_for_an_announced_unit_upstream():
+def test_loss_one_pass_gradient_for_an_announced_unit_upstream():
     """stj_loss_coef + stj_loss_fwd_bwd (OGMFlow_loss.unit_grad + prepare(), the captured train step's path) against the two-pass path
     stj_loss_fwd / stj_loss_bwd: same coefficients (bit for bit), same loss values, same d/dlogits; another upstream gradient than the
     announced tensor takes the general kernel."""
@@ -851,19 +851,11 @@ def test_loss_forward_writes_the_gradient_for_an_announced_unit_upstream():
                 assert torch.equal(gate3, gate) and torch.equal(coef3, coef)
             assert float(coef[4 * 5 + 2]) == 0.0 and (not use_gt or float(coef[4 * 3 + 3]) == 0.0)
             hits = ops.LOSS_FUSED_STATS['hits']
-            side = torch.cuda.Stream() if use_gt else None     # the loss values' finalize launch on a side stream (the caller joins it) | on the caller's
-            fn.finalize_stream = side
             fn.prepare(tw)
             lt.grad = None
-            ops.LOSS_FIN_SIDE, keep = True, ops.LOSS_FIN_SIDE        # (the switch is off in the shipped step: measured slower there)
-            try:
-                d1 = fn(get_pred_waypoint_logits(lt), tw, None)
-            finally:
-                ops.LOSS_FIN_SIDE = keep
+            d1 = fn(get_pred_waypoint_logits(lt), tw, None)
             d1.total.backward(one)
             assert ops.LOSS_FUSED_STATS['hits'] == hits + 1
-            if side is not None:
-                torch.cuda.current_stream().wait_stream(side)
             for k in ('observed_xe', 'occluded_xe', 'flow', 'flow_warp_xe'):
                 a, b = float(d1[k]), float(d0[k])
                 assert abs(a - b) <= 2e-6 * abs(b) + 1e-9, (flags, use_gt, k, a, b)          # f32 summation order of the partial sums
@@ -1213,7 +1205,7 @@ def test_upconv_add_fused_skip(dt, F_, Hi, Cin, Cout, two):
 
 @pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize('F_,Hi,Cin,Cout,two', [(3, 16, 192, 128, True), (2, 8, 384, 192, False)])
-def test_upconv_add_skips_pre_junction(dt, F_, Hi, Cin, Cout, two):
+def test_upconv_add_skips_pre_contract_bit_identical(dt, F_, Hi, Cin, Cout, two):
     """The decoder level whose skips are ELU outputs of linear_z (the time-collapsed Conv3D skips): upconv_add(skips_pre=True) + linear_z(grad_is_pre=True)
     -- ONE stj_skip_junction_bwd for the level's three ELU' products -- against the forms it replaces (stj_elu_res_bwd / the plain adds, then one
     stj_unary_bwd per skip): outputs and every gradient BIT-identical (the junction rounds where the separate passes rounded)."""
@@ -1231,15 +1223,10 @@ def test_upconv_add_skips_pre_junction(dt, F_, Hi, Cin, Cout, two):
         bs = [mk_param((Cout,), dt, 0.1, seed=30 + i) for i in range(len(ws))]
         x = x0.clone().requires_grad_(True)
         skin = [s0.clone().requires_grad_(True) for _ in ws]
-        keep, ops.SKIP_JUNCTION = ops.SKIP_JUNCTION, junction
-        try:
-            pre = ops.skips_pre_ok(dt)
-            assert pre == junction
-            sk = [ops.linear_z(si, w.master, w.c[0], Ci * Cout, b.master.detach(), 0, w.grad[0], Ci * Cout, b.grad, F_, act=ops.ACT_ELU, shared_x=True,
-                               grad_is_pre=pre) for si, w, b in zip(skin, ws, bs)]
-            out = ops.upconv_add(x, pw, pb, sk[0], sk[1] if two else None, skips_pre=pre)
-        finally:
-            ops.SKIP_JUNCTION = keep
+        assert ops.skips_pre_ok(dt)        # the training form of the 16-bit modes: the junction is what the model takes here
+        sk = [ops.linear_z(si, w.master, w.c[0], Ci * Cout, b.master.detach(), 0, w.grad[0], Ci * Cout, b.grad, F_, act=ops.ACT_ELU, shared_x=True,
+                           grad_is_pre=junction) for si, w, b in zip(skin, ws, bs)]
+        out = ops.upconv_add(x, pw, pb, sk[0], sk[1] if two else None, skips_pre=junction)
         y, y2 = out if two else (out, None)
         loss = (y.float() * g1.float()).sum() + ((y2.float() * g2.float()).sum() if two else 0.0)
         loss.backward()

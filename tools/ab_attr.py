@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Run bench.py with attributes of the model overridden after construction -- for same-box A/B runs of a switchable path.
-usage: tools/ab_attr.py fused_mlp_dims="(96,192)" fused_fgattn=False ops.SKIP_JUNCTION=False -- --no-cpu-baseline --no-extra-configs --no-kernel-timing
+usage: tools/ab_attr.py fused_mlp_dims="(96,192)" fused_fgattn=False ops.UPWG_BUDGET=192 -- --no-cpu-baseline --no-extra-configs --no-kernel-timing
 (name=value: attribute of the model; ops.NAME=value: module constant of strajnet_amd.ops)"""
 import os, sys, runpy
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
