@@ -371,19 +371,13 @@ class STrajNet:
         src, leaf = self._cut_src, self._cut_leaf
         self._cut_src = self._cut_leaf = None
         pairs = [(s_, l.grad) for s_, l in zip(src, leaf) if l.grad is not None]
-        ops.wgrad_queue_begin(self.device)    # the encoder's dense weight gradients: queued, flushed at the stage boundaries and here
+        sched = ops.wgrad_schedule(self.device)
+        sched.begin()                        # the encoder's dense weight gradients: queued, flushed at the stage boundaries and by the join
         try:
             torch.autograd.backward([a for a, _ in pairs], [g for _, g in pairs])
-            main = torch.cuda.current_stream(self.device)
-            for st in self._streams:
-                if st is not None:
-                    main.wait_stream(st)
         finally:
-            with torch.no_grad():
-                ops.wgrad_queue_end(self.device)
-        ops.wgrad_join_now(main)
-        with torch.no_grad():
-            self._fold_partials('encoder')
+            sched.join(torch.cuda.current_stream(self.device), [st for st in self._streams if st is not None],
+                       lambda: self._fold_partials('encoder'))
 
     def grads(self):
         return OrderedDict((n, p.grad) for n, p in self.params.items())
@@ -527,7 +521,7 @@ class STrajNet:
             r, c = self.stage_res[i], self.stage_dim[i]
             x, res = self._basic_layer(x, f'layers{i}', B, r, depths[i], heads[i], i < 2, add=joined_flow_x if i == 0 else None)
             if i < 2:       # in backward: stage i + 1 is through -> its weight gradients (and whatever else is queued) leave as one launch
-                x = ops.wgrad_queue_flush_point(x)
+                x = ops.wgrad_flush_point(x)
             if i == 0:
                 res_list.append(crop(flow_res, r, c) if self.large_ogm else flow_res)
                 if hook is not None:
@@ -852,7 +846,7 @@ class STrajNet:
                 raise RuntimeError('inputs must be CUDA (ROCm) tensors: the HIP path has no CPU fallback')
         self._side, self._side2 = (None, None) if self.serial else self._streams
         ops.set_serial(self.serial)
-        ops.wgrad_queue_reset(self.device)
+        ops.wgrad_schedule(self.device).reset()
         ops.use_arena(self._arena)
         self._sync_compute_weights()
         self._dctx = None
@@ -959,7 +953,7 @@ class STrajNet:
             with torch.cuda.stream(self._side2):
                 skips = (self._resconv(res_list[2], 'decoder/resconv_3', skips_pre), self._resconv(res_list[1], 'decoder/resconv_2', skips_pre),
                          self._resconv(res_list[0], 'decoder/resconv_f', skips_pre))
-        q = ops.wgrad_queue_flush_point(res_list[-1]).reshape(B, hb, hb, Cb)     # backward: FG-MSA / cross-attention / agent branch are through
+        q = ops.wgrad_flush_point(res_list[-1]).reshape(B, hb, hb, Cb)     # backward: FG-MSA / cross-attention / agent branch are through
         # waypoint-major [8,B,HW,Cb] (the reference's [B,8,...] transposed): every per-waypoint product downstream is then a
         # plain batched GEMM and the decoder frames are t-major; the output kernel undoes it when writing [B,H,W,32]
         if self.fg_msa:
@@ -980,10 +974,7 @@ class STrajNet:
         # the decoder's weight gradients are launched when ITS backward is through (ops.py).  (Flushing them only after the cross-attention
         # backward as well -- so that kernel has the GPU to itself -- measured 5 % SLOWER, 7.26 vs 6.88 ms: the 1.5 ms of half-GPU
         # weight-gradient launches then reach into the encoder's backward.)
-        x = ops.wgrad_flush_point(x)
-        try:
+        with ops.deferred_upconv_wgrads(x) as x:
             out = self._decoder(x, res_list, B, skips, skips_pre)
-        finally:
-            ops.wgrad_defer_end()        # (also when the decoder raises: a stale "defer" flag would swallow the next stand-alone up-conv's weight gradient)
         self._tap('output', out)
         return ops.join_after_backward(out, (self._side, self._side2), fold)

@@ -5,6 +5,7 @@ launch of a hand-written gfx950 kernel from libstrajnet_hip.so.  Weight gradient
 kernels straight into the model's flat f32 gradient buffer (the DP all-reduce bucket) -- autograd only
 routes activation gradients.
 """
+import contextlib
 import ctypes
 
 import os
@@ -206,13 +207,6 @@ def zeros_f32(shape, device):
     return v.view(shape)
 
 
-# ----------------------------------------------------------------------------------------------------
-# Weight gradients on a side stream.  In backward the data-gradient chain (dY -> dX -> ...) is the critical path; the weight
-# gradient of a layer (x^T dY, accumulated into the flat gradient buffer) is a leaf of the dependency graph.  Most kernels of
-# this model are latency-bound and leave CUs idle, so the wgrad launches go to a second stream that forks from the current one
-# (dY is complete) and is joined ONCE, when the autograd engine finishes the backward pass (queue_callback).  Operands stay
-# referenced until the join, so the caching allocator cannot hand their memory to later kernels of the main stream.
-# ----------------------------------------------------------------------------------------------------
 _ROLE_STREAMS = {}
 
 
@@ -231,9 +225,29 @@ def role_stream(device, role, priority=0):
     return st
 
 
-_WG = {}
-
-
+# ----------------------------------------------------------------------------------------------------
+# The weight-gradient schedule of a backward pass.  In backward the data-gradient chain (dY -> dX -> ...) is the critical path; the
+# weight gradient of a layer (x^T dY, accumulated into the flat gradient buffer) is a leaf of the dependency graph.  Where and when
+# those leaves are launched is decided by ONE object per device (_WgradSchedule), which owns:
+#   - the side stream.  Most kernels of this model are latency-bound and leave CUs idle, so the up-convs' weight gradients go to a
+#     second stream that forks from the current one (dY is complete) and is joined ONCE, when the autograd engine finishes the
+#     backward pass (queue_callback).  Operands stay referenced until the join, so the caching allocator cannot hand their memory
+#     to later kernels of the main stream.
+#   - the dense queue.  Inside a model's backward pass (between _JoinAfterBackward.backward, the first node the engine runs, and
+#     its end-of-pass callback) every dW += x^T dY that gemm() is asked for is QUEUED instead of launched; a flush (the model's
+#     flush points and the end of the pass) sends everything queued so far as one stj_wgrad_group launch per 28 problems.  The
+#     queue holds the operands; operands produced on another stream are ordered in front of the flush with an event and recorded
+#     on the flush stream.
+#   - the deferred up-convs.  Launched where they are produced, the six weight-gradient kernels of the decoder (1.1 ms of work)
+#     share HBM with the input-gradient chain they run next to (the 96 <- 48 dgrad takes 0.48 ms in the step, 0.31 ms alone) and
+#     are finished long before anybody needs them.  The model puts a flush point behind the decoder (in backward order): the
+#     kernels are queued there, on the side stream, under the cross-attention / FG-MSA backward -- a chain of short launches that
+#     leaves most of the GPU idle.  Whether an up-conv defers is decided when its FORWARD runs (ctx.defer) and only inside
+#     deferred_upconv_wgrads(): an up-conv applied outside it (op-level use, another graph) launches its weight gradient at once,
+#     whatever ran before.
+# One schedule per device (the autograd engine runs a device's backward nodes on that device's worker thread with the device
+# current): two models stepping on two GPUs of one process keep their work apart.
+# ----------------------------------------------------------------------------------------------------
 _SERIAL = False
 
 
@@ -243,56 +257,181 @@ def set_serial(flag):
     _SERIAL = bool(flag)
 
 
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
+WGRAD_SK = os.environ.get('STJ_WGRAD_SK', '1') != '0'
 
 
-def _wgrad_join(key):
-    st = _WG[key]
-    st['main'].wait_stream(st['side'])
-    st['keep'].clear()
-    st['armed'] = False
+class _WgradSchedule:
+    def __init__(self, idx):
+        self.idx = idx
+        self.side = None        # the side stream (role_stream(idx, 'wgrad')), made on first use
+        self.keep, self.armed, self.main = [], False, None      # operands of side-stream launches; a join callback is queued, for `main`
+        self.dense_on, self.jobs = False, []        # gemm() queues dense weight gradients: (job, post, stream, event)
+        self.defer, self.upconvs = False, []        # up-convs applied now defer their weight gradients: (wg, x, dpre)
+
+    def side_stream(self, *operands):
+        """Context manager: kernels launched inside run on the side stream (the up-convs' weight gradients only: measured at B=8,
+        up-convs on the side stream +1 %, dense layers -9 % -- their 768-block split-K kernels crowd the data-gradient chain out of
+        the CUs)."""
+        if _SERIAL:
+            return contextlib.nullcontext()
+        if self.side is None:
+            # (a low-priority side stream measured nothing: 1341 / 1360 / 1345 vs 1350 / 1363 / 1349 scenes/s)
+            self.side = role_stream(self.idx, 'wgrad')
+        main = torch.cuda.current_stream(self.idx)
+        self.side.wait_stream(main)
+        self.keep.extend(operands)
+        if not self.armed:
+            self.armed, self.main = True, main
+            torch.autograd.Variable._execution_engine.queue_callback(self._join_side)
+        return torch.cuda.stream(self.side)
+
+    def _join_side(self):
+        self.main.wait_stream(self.side)
+        self.keep.clear()
+        self.armed = False
+
+    def begin(self):
+        """Start of a backward pass: dense weight gradients are queued until the join."""
+        assert not self.jobs, 'wgrad schedule: jobs of another backward pass are still queued on this device'
+        self.dense_on = WGRAD_SK
+
+    def reset(self):
+        """Start of a forward pass: whatever an aborted backward pass left behind is dropped."""
+        self.dense_on, self.jobs = False, []
+
+    def push(self, job, post):
+        st = torch.cuda.current_stream(self.idx)
+        ev = None
+        if not _SERIAL:
+            ev = torch.cuda.Event()
+            ev.record(st)
+        self.jobs.append((job, post, st, ev))
+
+    def flush(self):
+        """Launch everything deferred so far: the up-convs on the side stream, then the dense queue on the current stream."""
+        self._flush_upconvs()
+        self._flush_dense()
+
+    # (Releasing the OLDEST deferred up-convs -- the 256 x 256 level's -- already at the two-skip level's junction, beside the junction and the two wide input-gradient
+    #  kernels that run alone there: 1 / 2 / 4 launches early 1352 / 1362 / 1355 scenes/s against 1380 with all of them deferred, profiles/r06_t_ab_upwg_early.txt.)
+    def _flush_upconvs(self):
+        items, self.upconvs = self.upconvs, []
+        if not items:
+            return
+        # Widest Cin first: they then run beside the thin FG-MSA / agent chain, and only the budgeted persistent launches reach into the
+        # encoder.  Round 6, alternating same-box runs: widest first 1372 / 1365 / 1359 scenes/s; in backward order (full-resolution layers
+        # first, the two wide layers 192 -> 128 / 384 -> 192 last: 1024-workgroup non-persistent launches that land on Swin stage 2's
+        # backward) 1350 / 1363 / 1349; reversed 1340 / 1351 / 1353.
+        items = sorted(items, key=lambda it: -it[1].shape[-1])        # (stable: equal widths keep their backward order)
+        with self.side_stream(*[t for it in items for t in it[1:]]):
+            for wg, _, _ in items:
+                wg()
+
+    def _flush_dense(self):
+        """On the current stream.  (Round 5: the flush-point launches on the weight-gradient side stream instead, so that the next
+        stage's backward need not wait for them, measured 1286-1291 scenes/s with all CUs as the launch's budget, 1270-1276 with 128
+        workgroups, 1234-1246 with 96, against 1296-1305 on the main stream: the Swin backward kernels they would run beside fill the CUs
+        they are given, and the join before the optimizer waits for the slowed-down last flush.)"""
+        items, self.jobs = self.jobs, []
+        if not items:
+            return
+        cur = torch.cuda.current_stream(self.idx)
+        last = {}
+        for job, post, st, ev in items:
+            if ev is not None and st != cur:
+                last[st] = ev                       # events of one stream are ordered: the last one covers the earlier ones
+                for t in (job.x, job.dy):
+                    if isinstance(t, torch.Tensor):
+                        t.record_stream(cur)
+        for ev in last.values():
+            cur.wait_event(ev)
+        wgrad_group([it[0] for it in items])
+        for _, post, _, _ in items:
+            if post is not None:
+                post()
+
+    def join(self, main, streams, post):
+        """End of a backward pass, on `main`: wait for `streams`, launch what is still queued (the dense weight gradients as one grouped
+        stream-K launch; up-convs of a flush point whose backward did not run), wait for the side stream, then run `post` (e.g. fold the
+        partial-gradient copies into the flat gradient buffer)."""
+        for s in streams:
+            main.wait_stream(s)
+        with torch.cuda.stream(main), torch.no_grad():
+            self._flush_dense()
+            self.dense_on = False
+            self._flush_upconvs()
+            # the side stream writes bias-gradient partials that `post` folds: it must be ordered before the fold (its own join callback
+            # is queued later than this one and would run after it).  Called after the pass (backward_encoder), it finds the side stream
+            # already joined by that callback.
+            if self.armed:
+                main.wait_stream(self.side)
+            if post is not None:
+                post()
+
+
+_SCHEDULES = {}
+
+
+def wgrad_schedule(dev=None):
+    """The schedule of `dev` (a torch.device; None: the calling thread's current device).  Callers that know their model's or tensor's
+    device pass it: the forward thread's current device need not be the model's (several GPUs driven by one process), while autograd's
+    worker thread of a device always has that device current."""
+    if dev is not None and getattr(dev, 'type', 'cuda') == 'cuda' and getattr(dev, 'index', None) is not None:
+        idx = dev.index
+    else:
+        idx = torch.cuda.current_device() if torch.cuda.is_available() else -1
+    s = _SCHEDULES.get(idx)
+    if s is None:
+        s = _SCHEDULES[idx] = _WgradSchedule(idx)
+    return s
 
 
 def wgrad_join_now(main):
     """Order `main` after everything queued on the weight-gradient side stream of main's device (used where a backward pass is
     followed by work the autograd engine's callbacks do not cover)."""
-    key = main.device.index if main.device.index is not None else torch.cuda.current_device()
-    st = _WG.get(key)
-    if st is not None:
-        main.wait_stream(st['side'])
+    side = wgrad_schedule(main.device).side
+    if side is not None:
+        main.wait_stream(side)
 
 
-def wgrad_stream(*operands):
-    """Context manager: kernels launched inside run on the weight-gradient side stream of the operands' device (the up-convs' weight
-    gradients only: measured at B=8, up-convs on the side stream +1 %, dense layers -9 % -- their 768-block split-K kernels crowd the
-    data-gradient chain out of the CUs)."""
-    if _SERIAL:
-        return _NullCtx()
-    dev = operands[0].device
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    st = _WG.get(key)
-    if st is None:
-        # (a low-priority side stream measured nothing: 1341 / 1360 / 1345 vs 1350 / 1363 / 1349 scenes/s)
-        st = _WG[key] = {'side': role_stream(dev, 'wgrad'), 'keep': [], 'armed': False, 'main': None}
-    main = torch.cuda.current_stream(dev)
-    st['side'].wait_stream(main)
-    st['keep'].extend(operands)
-    if not st['armed']:
-        st['armed'], st['main'] = True, main
-        torch.autograd.Variable._execution_engine.queue_callback(lambda: _wgrad_join(key))
-    return torch.cuda.stream(st['side'])
+class _FlushWgrads(torch.autograd.Function):
+    """Identity whose backward launches the deferred weight gradients: everything downstream of it in the forward pass has been through."""
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        wgrad_schedule(g.device).flush()
+        return g
+
+
+def wgrad_flush_point(x):
+    """Identity whose backward flushes the dense queue: a flush at every stage boundary, not only at the end of the pass (end only:
+    1.5 % slower end to end).  A no-op without the queue or without autograd."""
+    if WGRAD_SK and x.requires_grad and torch.is_grad_enabled():
+        return _FlushWgrads.apply(x)
+    return x
+
+
+@contextlib.contextmanager
+def deferred_upconv_wgrads(x):
+    """`with deferred_upconv_wgrads(x) as x:` -- the up-convs applied inside defer their weight gradients to a flush point on x, whose
+    backward launches them (and the dense weight gradients queued so far: the decoder's three time-kernel skips) when the region's
+    backward is through.  A no-op without autograd."""
+    s = wgrad_schedule(x.device)
+    s.defer, s.upconvs = x.requires_grad and torch.is_grad_enabled(), []
+    try:
+        yield _FlushWgrads.apply(x) if s.defer else x
+    finally:
+        s.defer = False      # (also when the region raises: a stale flag would swallow the next stand-alone up-conv's weight gradient)
 
 
 class _JoinAfterBackward(torch.autograd.Function):
-    """Identity on the model output.  Its backward is the FIRST node the engine runs; it queues a callback that makes the
-    stream backward was called from wait for the model's side streams once the whole pass has been enqueued -- gradients
-    written by side-stream kernels straight into the flat buffer (no AccumulateGrad node the engine could track) are then
-    ordered before whatever the caller enqueues next (optimizer, all-reduce, end of a graph capture)."""
+    """Identity on the model output.  Its backward is the FIRST node the engine runs; it opens the dense queue and queues a callback
+    that joins the pass once the whole pass has been enqueued (_WgradSchedule.join) -- gradients written by side-stream kernels
+    straight into the flat buffer (no AccumulateGrad node the engine could track) are then ordered before whatever the caller
+    enqueues next (optimizer, all-reduce, end of a graph capture)."""
     @staticmethod
     def forward(ctx, out, streams, post):
         ctx.streams, ctx.post = streams, post
@@ -302,24 +441,9 @@ class _JoinAfterBackward(torch.autograd.Function):
     def backward(ctx, g):
         streams, post = ctx.streams, ctx.post
         main = torch.cuda.current_stream(g.device)
-        wgrad_queue_begin(g.device)
-
-        def join():
-            for s in streams:
-                main.wait_stream(s)
-            with torch.cuda.stream(main), torch.no_grad():
-                wgrad_queue_end(g.device)     # the dense weight gradients still queued (one grouped stream-K launch)
-            # the weight-gradient side stream writes bias-gradient partials that `post` folds: it must be ordered before the fold
-            # (its own join callback is queued later than this one and would run after it)
-            key = g.device.index if g.device.index is not None else torch.cuda.current_device()
-            flush_upconv_wgrads()             # (leftovers: a flush point whose backward did not run)
-            st = _WG.get(key)
-            if st is not None and st['armed']:
-                main.wait_stream(st['side'])
-            if post is not None:          # e.g. fold the partial-gradient copies into the flat gradient buffer
-                with torch.cuda.stream(main), torch.no_grad():
-                    post()
-        torch.autograd.Variable._execution_engine.queue_callback(join)
+        s = wgrad_schedule(g.device)
+        s.begin()
+        torch.autograd.Variable._execution_engine.queue_callback(lambda: s.join(main, streams, post))
         return g, None, None
 
 
@@ -347,12 +471,12 @@ def gemm(A, B, C, M, N, K, sA, sB, sC, dt, bias=None, sBias=(0, 0), res=None, sR
     post: callable that consumes C; it travels with a DEFERRED weight gradient and runs behind the flush that carries it.
     Returns True when the product was queued (post will run), False when it was launched (or recorded in the open group): the
     caller then runs its post-processing itself, after closing the group."""
-    if (accumulate and isinstance(A, torch.Tensor) and isinstance(B, torch.Tensor) and _wq(A.device)['on'] and splitk == 0 and c_f32
+    if (accumulate and isinstance(A, torch.Tensor) and isinstance(B, torch.Tensor) and wgrad_schedule(A.device).dense_on and splitk == 0 and c_f32
             and kseg[0] == 1 and sA[2] == 1 and sB[3] == 1 and bias is None and res is None and alpha == 1.0):
         # a weight gradient dW += x^T dY inside a model's backward pass: queued for the grouped stream-K launch of the next flush
         j = WJob(A, B, C, colsum, K, M, N, sA[3], sB[2], sC[2], dt, nb=nb, sx=sA[:2], sdy=sB[:2], sdw=sC[:2], sdb=sBias)
         if j.supported():
-            wgrad_queue_push(j, post, A.device)
+            wgrad_schedule(A.device).push(j, post)
             return True
     _gemm_call(A, B, C, M, N, K, sA, sB, sC, dt, bias, sBias, res, sRes, nb, act, alpha, c_f32, accumulate, splitk, colsum, kseg)
     return False
@@ -426,104 +550,6 @@ def wgrad_group(jobs, budget=None):
         arr = (WgradJob * len(fast))(*[j.c() for j in fast])
         _WJ_LAST[0] = fast
         call('stj_wgrad_group', ctypes.cast(arr, vp), len(fast), fast[0].dt, WG_BUDGET if budget is None else budget, _st())
-
-
-# Deferred weight gradients.  Inside a model's backward pass (between _JoinAfterBackward.backward, the first node the engine runs, and its
-# end-of-pass callback) every dW += x^T dY that gemm() is asked for is QUEUED instead of launched; a flush (the model's flush points and
-# the end of the pass) sends everything queued so far as one stj_wgrad_group launch per 28 problems.  The queue holds the operands, so
-# the caching allocator cannot recycle them before the flush is enqueued; operands produced on another stream are ordered in front of
-# the flush with an event and recorded on the flush stream.
-WGRAD_SK = os.environ.get('STJ_WGRAD_SK', '1') != '0'
-class _WQueues(dict):
-    """One queue per device (the autograd engine runs a device's backward nodes on that device's worker thread with the device
-    current): two models stepping on two GPUs of one process keep their queued jobs apart."""
-    def __missing__(self, dev):
-        q = self[dev] = {'on': False, 'jobs': []}
-        return q
-
-
-_WQS = _WQueues()
-
-
-def _wq(dev=None):
-    """The queue of `dev` (a torch.device / tensor device; None: the calling thread's current device).  Callers that know their model's or
-    tensor's device pass it: the forward thread's current device need not be the model's (several GPUs driven by one process), while
-    autograd's worker thread of a device always has that device current."""
-    if dev is not None and getattr(dev, 'type', 'cuda') == 'cuda' and getattr(dev, 'index', None) is not None:
-        return _WQS[dev.index]
-    return _WQS[torch.cuda.current_device() if torch.cuda.is_available() else -1]
-
-
-def wgrad_queue_begin(dev=None):
-    q = _wq(dev)
-    assert not q['jobs'], 'wgrad_queue_begin: jobs of another backward pass are still queued on this device'
-    q['on'] = WGRAD_SK
-
-
-def wgrad_queue_reset(dev=None):
-    """Start of a forward pass: whatever an aborted backward pass left behind is dropped."""
-    q = _wq(dev)
-    q['on'] = False
-    q['jobs'] = []
-
-
-def wgrad_queue_push(job, post=None, dev=None):
-    st = torch.cuda.current_stream(dev)
-    ev = None
-    if not _SERIAL:
-        ev = torch.cuda.Event()
-        ev.record(st)
-    _wq(dev)['jobs'].append((job, post, st, ev))
-
-
-def wgrad_queue_flush(dev=None):
-    """Launch everything queued (on `dev`; None: the current device), on the current stream.  (Round 5: the flush-point launches on the weight-gradient side stream instead,
-    so that the next stage's backward need not wait for them, measured 1286-1291 scenes/s with all CUs as the launch's budget, 1270-1276
-    with 128 workgroups, 1234-1246 with 96, against 1296-1305 on the main stream: the Swin backward kernels they would run beside fill
-    the CUs they are given, and the join before the optimizer waits for the slowed-down last flush.)"""
-    q = _wq(dev)
-    items, q['jobs'] = q['jobs'], []
-    if not items:
-        return
-    cur = torch.cuda.current_stream(dev)
-    last = {}
-    for job, post, st, ev in items:
-        if ev is not None and st != cur:
-            last[st] = ev                       # events of one stream are ordered: the last one covers the earlier ones
-            for t in (job.x, job.dy):
-                if isinstance(t, torch.Tensor):
-                    t.record_stream(cur)
-    for ev in last.values():
-        cur.wait_event(ev)
-    wgrad_group([it[0] for it in items])
-    for _, post, _, _ in items:
-        if post is not None:
-            post()
-
-
-def wgrad_queue_end(dev=None):
-    wgrad_queue_flush(dev)
-    _wq(dev)['on'] = False
-
-
-class _WgradQueueFlush(torch.autograd.Function):
-    """Identity whose backward flushes the weight-gradient queue: everything downstream of it in the forward pass has been through."""
-    @staticmethod
-    def forward(ctx, x):
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        wgrad_queue_flush(g.device)
-        return g
-
-
-def wgrad_queue_flush_point(x):
-    """Identity whose backward flushes the weight-gradient queue: a flush at every stage boundary, not only at the end of the pass (end
-    only: 1.5 % slower end to end)."""
-    if WGRAD_SK and x.requires_grad and torch.is_grad_enabled():
-        return _WgradQueueFlush.apply(x)
-    return x
 
 
 def _splitk(M_out, N_out, Kdim):
@@ -2156,63 +2182,13 @@ def _upconv_backward_tail(ctx, x, dpre, wd, need_dx):
         call('stj_upconv_fold', _p(dweff), _p(pw.grad), Cin, Cout, _st())
         if own:
             pb.grad.add_(dbp.view(nparts, Cout).sum(0))
+    s = wgrad_schedule(x.device)
     if ctx.defer and not _SERIAL:
-        _UPWG['items'].append((wg, x, dpre))             # launched by flush_upconv_wgrads() (the model's flush point)
+        s.upconvs.append((wg, x, dpre))             # launched by the flush point of deferred_upconv_wgrads()
     else:
-        with wgrad_stream(x, dpre):
+        with s.side_stream(x, dpre):
             wg()
     return dx
-
-
-# Deferred up-conv weight gradients.  Launched where they are produced, the six weight-gradient kernels of the decoder (1.1 ms of work) share
-# HBM with the input-gradient chain they run next to (the 96 <- 48 dgrad takes 0.48 ms in the step, 0.31 ms alone) and are finished long before
-# anybody needs them.  The model puts a flush point behind the decoder (in backward order): the kernels are queued there, on the side stream,
-# under the cross-attention / FG-MSA backward -- a chain of short launches that leaves most of the GPU idle.
-# Whether an up-conv defers is decided when its FORWARD runs (ctx.defer) and only between wgrad_flush_point() and wgrad_defer_end():
-# an up-conv applied outside that region (op-level use, another graph) launches its weight gradient at once, whatever ran before.
-_UPWG = {'on': False, 'items': []}
-
-
-# (Releasing the OLDEST deferred launches -- the 256 x 256 level's -- already at the two-skip level's junction, beside the junction and the two wide input-gradient
-#  kernels that run alone there: 1 / 2 / 4 launches early 1352 / 1362 / 1355 scenes/s against 1380 with all of them deferred, profiles/r06_t_ab_upwg_early.txt.)
-def flush_upconv_wgrads():
-    items, _UPWG['items'] = _UPWG['items'], []
-    if not items:
-        return
-    # Widest Cin first: they then run beside the thin FG-MSA / agent chain, and only the budgeted persistent launches reach into the
-    # encoder.  Round 6, alternating same-box runs: widest first 1372 / 1365 / 1359 scenes/s; in backward order (full-resolution layers
-    # first, the two wide layers 192 -> 128 / 384 -> 192 last: 1024-workgroup non-persistent launches that land on Swin stage 2's
-    # backward) 1350 / 1363 / 1349; reversed 1340 / 1351 / 1353.
-    items = sorted(items, key=lambda it: -it[1].shape[-1])        # (stable: equal widths keep their backward order)
-    with wgrad_stream(*[t for it in items for t in it[1:]]):
-        for wg, _, _ in items:
-            wg()
-
-
-class _WgradFlushPoint(torch.autograd.Function):
-    """Identity.  Everything downstream of it in the forward pass has finished its backward when this node's backward runs."""
-    @staticmethod
-    def forward(ctx, x):
-        return x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, g):
-        flush_upconv_wgrads()
-        wgrad_queue_flush(g.device)     # the decoder's dense weight gradients (the three time-kernel skips)
-        return g
-
-
-def wgrad_flush_point(x):
-    """Mark x as the input of the region whose up-conv weight gradients are deferred (no-op without autograd).
-    The region ends at wgrad_defer_end()."""
-    _UPWG['on'] = x.requires_grad and torch.is_grad_enabled()
-    _UPWG['items'] = []
-    return _WgradFlushPoint.apply(x) if _UPWG['on'] else x
-
-
-def wgrad_defer_end():
-    """End of the forward region opened by wgrad_flush_point(): up-convs applied from here on do not defer."""
-    _UPWG['on'] = False
 
 
 class _UpConv(torch.autograd.Function):
@@ -2231,7 +2207,7 @@ class _UpConv(torch.autograd.Function):
         call('stj_upconv_fwd', _p(x), _p(wf), _p(pb.master), _p(y), F_, Hi, Wi, Cin, Cout, ACT_ELU, dt, _st())
         ctx.pw, ctx.pb, ctx.geo = pw, pb, (F_, Hi, Wi, Cin, Cout)
         ctx.grad_is_pre, ctx.x_is_elu_out = grad_is_pre, x_is_elu_out
-        ctx.defer = _UPWG['on']
+        ctx.defer = wgrad_schedule(x.device).defer
         ctx.save_for_backward(x, y, wd)
         return y
 
@@ -2271,7 +2247,7 @@ class _UpConvAdd(torch.autograd.Function):
         ctx.save_for_backward(x, y, r1, wd)
         ctx.pw, ctx.pb, ctx.geo = pw, pb, (F_, Hi, Wi, Cin, Cout)
         ctx.x_is_elu_out, ctx.two = False, r2 is not None
-        ctx.defer = _UPWG['on']
+        ctx.defer = wgrad_schedule(x.device).defer
         return (y, y2) if r2 is not None else y
 
     @staticmethod
@@ -2316,7 +2292,7 @@ class _UpConvSkips(torch.autograd.Function):
         y2 = y1 + r2 if r2 is not None else None
         ctx.pw, ctx.pb, ctx.geo = pw, pb, (F_, Hi, Wi, Cin, Cout)
         ctx.x_is_elu_out = False
-        ctx.defer = _UPWG['on']
+        ctx.defer = wgrad_schedule(x.device).defer
         ctx.skips_pre, ctx.two = skips_pre, r2 is not None
         if skips_pre:
             ctx.save_for_backward(x, y, wd, r1.contiguous(), r2.contiguous() if r2 is not None else None)

@@ -132,7 +132,7 @@ def test_same_parameter_twice_and_unsupported_shapes_fall_back():
         assert (j.dw.double() - ref).abs().max().item() <= 2e-3 * ref.abs().max().item()
 
 
-def test_deferred_queue_in_a_backward_pass_matches_immediate_launches():
+def test_wgrad_schedule_dense_queue_matches_immediate_launches():
     """The same Dense layers with the queue on (STJ_WGRAD_SK default: weight gradients leave at the flush) and off: identical gradients
     up to f32 summation order; and outside a model's backward pass nothing is ever deferred."""
     from strajnet_amd import ops
@@ -148,7 +148,7 @@ def test_deferred_queue_in_a_backward_pass_matches_immediate_launches():
             y = ops.join_after_backward(y, (), lambda: None)      # the node a model's output passes through: opens / closes the queue
         y.backward(rnd((4096, 96), dt, 6))
         torch.cuda.synchronize()
-        assert not ops._wq()['on'] and not ops._wq()['jobs']
+        assert not ops.wgrad_schedule().dense_on and not ops.wgrad_schedule().jobs
         grads.append([t.grad.clone() for t in (pw, pb, pw2, pb2)] + [x.grad.float().clone()])
     for a, b in zip(*grads):
         assert (a - b).abs().max().item() <= 1e-5 * max(1.0, b.abs().max().item()), (a - b).abs().max().item()
