@@ -400,6 +400,15 @@ int stj_upconv_fwd_head(const void* X, const void* Wf, const float* bias, const 
                         int Cout, int dtype, hipStream_t stream);
 int stj_outconv_pair_gather(const void* Z0, const void* Z1, const float* bias0, const float* bias1, float* Y, int B, int Tn, int H, int W,
                             int t_major, int dtype, hipStream_t stream);
+/* Challenge-format quantisation of the model output (inference.py:160-182).  Y [B,H,W,4*Tn] f32 logits, channel 4 t + {obs, occ,
+ * flow_x, flow_y}; Q one contiguous block of 4*Tn*H*W bytes per scene: [ obs u8 [Tn,H,W] | occ u8 [Tn,H,W] | flow i8 [Tn,H,W,2] ], so
+ * the slice of (scene, waypoint, field) is what the reference's .tobytes() yields for a batch of one.  obs / occ = (uint8)
+ * rintf(255 * sigmoid(x)), sigmoid in f32 with the accurate expf and an IEEE division; flow = (int8) clamp(rintf(x), -128, 127); rintf
+ * = round-half-to-even = np.round.  A NaN input is written as 0.  Tn = 8, H * W a multiple of 256, 16-byte aligned buffers;
+ * STJ_EUNSUPPORTED otherwise.  stj_outconv_pair_gather_q: stj_outconv_pair_gather (same sums, bit for bit) whose epilogue writes Q. */
+int stj_quantize_waypoints(const float* Y, uint8_t* Q, int B, int Tn, int H, int W, hipStream_t stream);
+int stj_outconv_pair_gather_q(const void* Z0, const void* Z1, const float* bias0, const float* bias1, uint8_t* Q, int B, int Tn, int H,
+                              int W, int t_major, int dtype, hipStream_t stream);
 int stj_outconv_bwd(const void* X, const float* W, const float* dY, void* dX, float* dW, float* db, int F, int Hh, int Ww,
                     int C, int Tn, long long y_bstride, long long y_tstride, long long y_pstride, int elu_in, void* ws,
                     long long ws_bytes, int dtype, hipStream_t stream);

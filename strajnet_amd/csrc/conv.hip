@@ -894,6 +894,8 @@ bool upconv_fwd_head_try(const void* X, const void* Wf, const float* bias, const
                          hipStream_t st);
 bool outconv_pair_gather_try(const void* Z0, const void* Z1, const float* b0, const float* b1, float* Y, int B, int Tn, int Hh, int Ww, int t_major,
                              int dtype, hipStream_t st);
+bool outconv_pair_gather_q_try(const void* Z0, const void* Z1, const float* b0, const float* b1, uint8_t* Q, int B, int Tn, int Hh, int Ww, int t_major,
+                               int dtype, hipStream_t st);
 extern "C" int stj_upconv_fwd_head(const void* X, const void* Wf, const float* bias, const float* Whead, void* Z, int F, int Hi, int Wi, int Cin,
                                    int Cout, int dtype, hipStream_t stream) {
   int e = upconv_check(F, Hi, Wi, Cin, Cout, dtype);
@@ -909,6 +911,15 @@ extern "C" int stj_outconv_pair_gather(const void* Z0, const void* Z1, const flo
   if (stj_is16(dtype) && outconv_pair_gather_try(Z0, Z1, bias0, bias1, Y, B, Tn, Hh, Ww, t_major, dtype, stream))
     return stj_check_launch("stj_outconv_pair_gather");
   stj_set_error("outconv_pair_gather: shape / dtype not covered");
+  return STJ_EUNSUPPORTED;
+}
+// stj_outconv_pair_gather whose epilogue writes the challenge-format bytes of stj_quantize_waypoints instead of the f32 line
+extern "C" int stj_outconv_pair_gather_q(const void* Z0, const void* Z1, const float* bias0, const float* bias1, uint8_t* Q, int B, int Tn, int Hh,
+                                         int Ww, int t_major, int dtype, hipStream_t stream) {
+  if (B <= 0 || Tn <= 0) { stj_set_error("outconv_pair_gather_q: empty problem"); return STJ_EINVAL; }
+  if (stj_is16(dtype) && outconv_pair_gather_q_try(Z0, Z1, bias0, bias1, Q, B, Tn, Hh, Ww, t_major, dtype, stream))
+    return stj_check_launch("stj_outconv_pair_gather_q");
+  stj_set_error("outconv_pair_gather_q: shape / dtype not covered");
   return STJ_EUNSUPPORTED;
 }
 // ws: caller-owned scratch of stj_outconv_bwd_workspace_bytes() bytes (need not be zeroed; per-block dW/db partials of the bf16

@@ -12,6 +12,7 @@
 //     the MFMA loop and written to the other LDS buffer after it;
 //   * results (bias + ELU applied) are staged in LDS and leave as full rows of 8-byte segments, coalesced.
 #include "common.h"
+#include "quantize.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -1133,10 +1134,13 @@ bool outconv_pair_fwd_try(const void* X0, const void* X1, const float* W0, const
 // tensors [F, H, W, HEAD_CZ = 20] of the two decoder branches.  A workgroup owns a 16 x 16 spatial tile of one scene and walks its 16 (waypoint,
 // head) planes through an 18 x 18 halo in LDS (next plane prefetched in registers); a thread keeps the 32 results of its pixel and writes
 // one full 128-byte line.
-template <typename T>
+// QUANT (stj_outconv_pair_gather_q): the same sums, but the epilogue turns the 32 results into the challenge format's bytes (quantize.h)
+// and Y is the byte buffer of stj_quantize_waypoints, [B][obs u8 [8,H,W] | occ u8 [8,H,W] | flow i8 [8,H,W,2]]: the tile's 32 plane
+// pieces (16 rows x 16 B, flow 32 B) are staged in the halo's LDS, which the last plane has finished with, and leave as 16-byte vectors.
+template <typename T, bool QUANT>
 __global__ __launch_bounds__(256) void outconv_pair_gather_kernel(const T* __restrict__ Z0, const T* __restrict__ Z1, const float* __restrict__ b0,
-                                                                  const float* __restrict__ b1, float* __restrict__ Y, int B, int Hh, int Ww,
-                                                                  int t_major, int nsp) {
+                                                                  const float* __restrict__ b1, std::conditional_t<QUANT, uint8_t, float>* __restrict__ Y,
+                                                                  int B, int Hh, int Ww, int t_major, int nsp) {
   constexpr int CZ = HEAD_CZ, LDZ = HEAD_CZ, CPP = CZ / 4, NPX = OCM_H * OCM_H, NCHK = NPX * CPP, NCH = (NCHK + 255) / 256;      // 8-byte pieces
   __shared__ __attribute__((aligned(16))) T halo[NPX * LDZ];
   const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
@@ -1161,6 +1165,7 @@ __global__ __launch_bounds__(256) void outconv_pair_gather_kernel(const T* __res
       }
     };
     float out[32];
+    uint32_t qb[8] = {0, 0, 0, 0, 0, 0, 0, 0};           // QUANT: the bytes of waypoint t, obs | occ << 8 | flow_x << 16 | flow_y << 24
     fetch(0);
 #pragma unroll 1
     for (int plane = 0; plane < 16; ++plane) {
@@ -1184,25 +1189,65 @@ __global__ __launch_bounds__(256) void outconv_pair_gather_kernel(const T* __res
           s0 += a0; s1 += a1;
         }
       // plane = 2 t + h -> channels 4 t + 2 h + {0, 1} = 2 plane + {0, 1}
+      if constexpr (QUANT) {       // quantised here, not behind the loop: 8 packed registers live instead of 32 floats
+        const uint32_t v = h ? (quant_flow(s0) | (quant_flow(s1) << 8)) << 16 : quant_prob(s0) | (quant_prob(s1) << 8);
 #pragma unroll
-      for (int q = 0; q < 16; ++q)
-        if (q == plane) { out[2 * q] = s0; out[2 * q + 1] = s1; }
+        for (int q = 0; q < 8; ++q)
+          if (q == (plane >> 1)) qb[q] |= v;
+      } else {
+#pragma unroll
+        for (int q = 0; q < 16; ++q)
+          if (q == plane) { out[2 * q] = s0; out[2 * q + 1] = s1; }
+      }
     }
-    float* yp = Y + (((long long)b * Hh + tcy * OCM_T + ty) * Ww + tcx * OCM_T + tx) * 32;
+    if constexpr (QUANT) {
+      static_assert(sizeof(halo) >= 32 * OCM_T * OCM_T, "the byte stage lives in the halo");
+      uint8_t* stg = reinterpret_cast<uint8_t*>(halo);           // [obs 8 x 256 | occ 8 x 256 | flow 8 x 512], a plane piece = 16 rows of the tile
+      __syncthreads();                                           // the last plane's reads are through
 #pragma unroll
-    for (int q = 0; q < 8; ++q) *reinterpret_cast<float4*>(yp + 4 * q) = make_float4(out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
+      for (int t = 0; t < 8; ++t) {
+        stg[t * 256 + tid] = (uint8_t)qb[t];
+        stg[2048 + t * 256 + tid] = (uint8_t)(qb[t] >> 8);
+        *reinterpret_cast<uint16_t*>(stg + 4096 + t * 512 + 2 * tid) = (uint16_t)(qb[t] >> 16);
+      }
+      __syncthreads();                                           // (the next tile's first halo write waits behind the barrier at the head of its plane loop)
+      const long long HW = (long long)Hh * Ww;
+      uint8_t* q = Y + (long long)b * 32 * HW;
+      const long long cell = (long long)(tcy * OCM_T) * Ww + tcx * OCM_T;
+      {       // threads 0..127: (observed plane, row), 128..255: (occluded plane, row): 16 B each
+        const int p = tid >> 4, r = tid & 15;
+        *reinterpret_cast<uint4*>(q + p * HW + cell + (long long)r * Ww) = *reinterpret_cast<const uint4*>(stg + 16 * tid);
+      }
+      {       // flow: (plane, row, half of the row's 32 B)
+        const int p = tid >> 5, r = (tid >> 1) & 15, hf = tid & 1;
+        *reinterpret_cast<uint4*>(q + 16 * HW + p * 2 * HW + 2 * (cell + (long long)r * Ww) + 16 * hf) = *reinterpret_cast<const uint4*>(stg + 4096 + 16 * tid);
+      }
+    } else {
+      float* yp = Y + (((long long)b * Hh + tcy * OCM_T + ty) * Ww + tcx * OCM_T + tx) * 32;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) *reinterpret_cast<float4*>(yp + 4 * q) = make_float4(out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]);
+    }
   }
 }
-bool outconv_pair_gather_try(const void* Z0, const void* Z1, const float* b0, const float* b1, float* Y, int B, int Tn, int Hh, int Ww, int t_major,
-                             int dtype, hipStream_t st) {
+template <bool QUANT>
+static bool outconv_pair_gather_launch(const void* Z0, const void* Z1, const float* b0, const float* b1, std::conditional_t<QUANT, uint8_t, float>* Y, int B,
+                                       int Tn, int Hh, int Ww, int t_major, int dtype, hipStream_t st) {
   if (Tn != 8 || Hh % OCM_T || Ww % OCM_T || (((uintptr_t)Y | (uintptr_t)Z0 | (uintptr_t)Z1) & 15)) return false;
   const int nsp = B * (Hh / OCM_T) * (Ww / OCM_T);
   const int nb = nsp < 2048 ? nsp : 2048;
   if (dtype == STJ_F16)
-    hipLaunchKernelGGL(outconv_pair_gather_kernel<f16>, dim3(nb), dim3(256), 0, st, (const f16*)Z0, (const f16*)Z1, b0, b1, Y, B, Hh, Ww, t_major, nsp);
+    hipLaunchKernelGGL((outconv_pair_gather_kernel<f16, QUANT>), dim3(nb), dim3(256), 0, st, (const f16*)Z0, (const f16*)Z1, b0, b1, Y, B, Hh, Ww, t_major, nsp);
   else
-    hipLaunchKernelGGL(outconv_pair_gather_kernel<bf16>, dim3(nb), dim3(256), 0, st, (const bf16*)Z0, (const bf16*)Z1, b0, b1, Y, B, Hh, Ww, t_major, nsp);
+    hipLaunchKernelGGL((outconv_pair_gather_kernel<bf16, QUANT>), dim3(nb), dim3(256), 0, st, (const bf16*)Z0, (const bf16*)Z1, b0, b1, Y, B, Hh, Ww, t_major, nsp);
   return true;
+}
+bool outconv_pair_gather_try(const void* Z0, const void* Z1, const float* b0, const float* b1, float* Y, int B, int Tn, int Hh, int Ww, int t_major,
+                             int dtype, hipStream_t st) {
+  return outconv_pair_gather_launch<false>(Z0, Z1, b0, b1, Y, B, Tn, Hh, Ww, t_major, dtype, st);
+}
+bool outconv_pair_gather_q_try(const void* Z0, const void* Z1, const float* b0, const float* b1, uint8_t* Q, int B, int Tn, int Hh, int Ww, int t_major,
+                               int dtype, hipStream_t st) {
+  return outconv_pair_gather_launch<true>(Z0, Z1, b0, b1, Q, B, Tn, Hh, Ww, t_major, dtype, st);
 }
 
 // Backward.  Occupancy is what matters here (the first MFMA version held all 27 (tap, channel-block) dW accumulators in every

@@ -246,10 +246,12 @@ class STrajNet:
         self.fused_xattn = True
         self.fused_stem = True         # PatchEmbed + the stem's sums / norms as one launch per raster (csrc/patch_embed.hip); False = im2col + dense + LayerNorm launches
         self.agent_override = None            # (key, mask) from agent_encode(): call() then skips the agent branch
+        self._quantize_heads = False          # set by predict_quantized() around its forward: the inference heads write the challenge format's bytes
         self.mid_forward_hook = None          # callable run once per forward pass behind the encoder's first stage (GraphedTrainStep: loss.prepare on its side stream)
         self.fused_fgattn = True       # FG-MSA attention core as one kernel per direction (8 x 8 / 16 x 16 maps; all three storage types)
         self.fused_agent = True        # TrajEncoder of all agents as one kernel per direction (csrc/agent_fused.hip); False = the layer-by-layer chain
         self.fused_agent_int = True    # ... and the 64-agent interaction block (16-bit storage types)
+        self.fused_quantize = True     # predict_quantized on the inference heads' path: quantise in the gather's epilogue; False = stj_quantize_waypoints behind it (the A/B of tools/bench_submission.py)
         self.fused_fgoff = True        # FG-MSA's offset head (conv_offset -> tanh * range) as one kernel per direction (csrc/fgoff_fused.hip)
         self._agent_pack = None
         self._agent_pack_event = None
@@ -803,6 +805,8 @@ class STrajNet:
             # 5555 / 5539 / 5341 / 5422 vs 5482 / 5317 / 5320 / 5337 and 5338 / 5452 / 5459 vs 5274 / 5378 / 5444 scenes/s)
             zo = last(x, 'decoder/upconv_1_0', 'decoder/upconv_0_0', oc[0])
             zf = last(fx, 'decoder/upconvf_1_0', 'decoder/upconvf_0_0', oc[2])
+            if self._quantize_heads and self.fused_quantize:         # predict_quantized: the challenge format's bytes straight from the gather's registers
+                return ops.heads_gather_q(zo, zf, self._p(oc[1]), self._p(oc[3]), B, 8, t_major=True)
             return ops.heads_gather(zo, zf, self._p(oc[1]), self._p(oc[3]), B, 8, t_major=True)
         # the last two levels of each branch have a single consumer, whose backward folds ELU' into the gradient it returns
         if self._side2 is not None:      # the observed-occupancy and flow branches of the last two levels are independent
@@ -826,6 +830,23 @@ class STrajNet:
     # ------------------------------------------------------------------ call
     def __call__(self, ogm, map_img, training=True, obs=None, occ=None, mapt=None, flow=None, dense_vec=None, dense_map=None):
         return self.call(ogm, map_img, training, obs, occ, mapt, flow, dense_vec, dense_map)
+
+    def predict_quantized(self, ogm, map_img, obs=None, occ=None, mapt=None, flow=None):
+        """Inference forward (training=False, no autograd) whose result is the challenge format's bytes (submission.QuantizedWaypoints;
+        reference inference.py:153-182: the model call + the quantisation of _add_waypoints_to_scenario_prediction).  Where the inference
+        form of the heads applies (ops.upconv_head_ok) the gather kernel quantises in its epilogue and the float32 output never exists;
+        otherwise (f32 parity mode, taps set, other shapes) stj_quantize_waypoints runs behind the ordinary output."""
+        from .submission import QuantizedWaypoints, quantize_waypoints
+        with torch.no_grad():
+            self._quantize_heads = True
+            try:
+                out = self.call(ogm, map_img, False, obs, occ, mapt, flow)
+            finally:
+                self._quantize_heads = False
+            if out.dtype == torch.uint8:
+                H = self.cfg['input_size'][0]
+                return QuantizedWaypoints(out, H, H)
+            return quantize_waypoints(out)
 
     def call(self, ogm, map_img, training=True, obs=None, occ=None, mapt=None, flow=None, dense_vec=None, dense_map=None):
         """STrajNet.call (modules.py:815-839).  mapt is ignored (actor_only=True), as in the reference."""

@@ -2457,6 +2457,15 @@ def heads_gather(zo, zf, p1b, p2b, B, Tn, t_major=False):
     return out
 
 
+def heads_gather_q(zo, zf, p1b, p2b, B, Tn, t_major=False):
+    """heads_gather whose epilogue quantises: uint8 [B, 4*Tn*H*W] in the challenge format's layout (stj_outconv_pair_gather_q; the
+    float sums are those of heads_gather bit for bit, the bytes those of stj_quantize_waypoints on them)."""
+    F_, H, W, _ = zo.shape
+    q = torch.empty((B, 4 * Tn * H * W), dtype=torch.uint8, device=zo.device)
+    call('stj_outconv_pair_gather_q', _p(zo), _p(zf), _p(p1b.master), _p(p2b.master), _p(q), B, Tn, H, W, 1 if t_major else 0, _dt(zo), _st())
+    return q
+
+
 def outconv_pair(xo, xf, p1w, p1b, p2w, p2b, B, Tn, t_major=False, x_is_elu_out=False, side=None):
     """side: the stream the second branch (xf) was computed on, when the caller runs the two branches on two streams."""
     return _OutConvPair.apply(xo, xf, p1w.master, p1b.master, p2w.master, p2b.master, p1w, p1b, p2w, p2b, B, Tn, t_major, x_is_elu_out, side)

@@ -84,6 +84,18 @@ def _pair_gather(a):
     return f'outconv_pair_gather[{H}x{W},F{B * Tn}x2]', 'outconv_fwd', 2.0 * 18 * 2 * B * Tn * H * W, 0.0, 2 * _es(dt) * B * Tn * H * W * 20 + 4 * B * H * W * 4 * Tn
 
 
+def _pair_gather_q(a):
+    """stj_outconv_pair_gather_q: the same sums; 4 bytes per cell and waypoint written instead of 16."""
+    B, Tn, H, W, dt = a[5], a[6], a[7], a[8], a[10]
+    return f'outconv_pair_gather_q[{H}x{W},F{B * Tn}x2]', 'outconv_fwd', 2.0 * 18 * 2 * B * Tn * H * W, 0.0, 2 * _es(dt) * B * Tn * H * W * 20 + B * H * W * 4 * Tn
+
+
+def _quantize(a):
+    """stj_quantize_waypoints(Y, Q, B, Tn, H, W, stream): 16 Tn bytes read + 4 Tn written per cell."""
+    B, Tn, H, W = a[2], a[3], a[4], a[5]
+    return f'quantize_waypoints[{H}x{W},B{B}]', 'quantize', 0.0, 0.0, 20 * Tn * B * H * W
+
+
 def _upconv_res(a):
     F, Hi, Wi, Cin, Cout, dt = a[7], a[8], a[9], a[10], a[11], a[12]
     es = _es(dt)
@@ -188,7 +200,7 @@ def _ln_chain(a):
 MODELS = {
     'stj_gemm': _gemm,
     'stj_patch_embed_fwd': _patch_embed, 'stj_layernorm_bwd_chain': _ln_chain,
-    'stj_upconv_fwd': _upconv('fwd'), 'stj_upconv_fwd_head': _upconv_head, 'stj_outconv_pair_gather': _pair_gather, 'stj_upconv_fwd_res': _upconv_res, 'stj_elu_res_bwd': _elu_res, 'stj_upconv_dgrad': _upconv('dgrad'), 'stj_upconv_wgrad': _upconv('wgrad'),
+    'stj_upconv_fwd': _upconv('fwd'), 'stj_upconv_fwd_head': _upconv_head, 'stj_outconv_pair_gather': _pair_gather, 'stj_outconv_pair_gather_q': _pair_gather_q, 'stj_quantize_waypoints': _quantize, 'stj_upconv_fwd_res': _upconv_res, 'stj_elu_res_bwd': _elu_res, 'stj_upconv_dgrad': _upconv('dgrad'), 'stj_upconv_wgrad': _upconv('wgrad'),
     'stj_outconv_fwd': _outconv('fwd'), 'stj_outconv_pair_fwd': _outconv_pair, 'stj_outconv_bwd': _outconv('bwd'),
     'stj_layernorm_fwd': _ln('fwd'), 'stj_layernorm_bwd': _ln('bwd'), 'stj_layernorm_res_fwd': _ln('res_fwd'),
     'stj_win_attn_fwd': _win('fwd'), 'stj_win_attn_bwd': _win('bwd'),
