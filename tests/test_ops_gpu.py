@@ -91,8 +91,9 @@ def _lib(lib_built):
 @pytest.mark.parametrize('dt', DTYPES)
 @pytest.mark.parametrize('M,K,N,act,use_res', [(300, 96, 288, 0, False), (1000, 384, 96, 0, True), (77, 5, 64, 2, False),
                                                (64, 2, 384, 0, False), (513, 384, 126, 0, False), (4096, 96, 48, 2, False),
-                                               # row-streaming kernel (bf16, M >= 2048, K in {96,128,192,288,384}): fwd [K,N] and dgrad [N,K] forms,
-                                               # ragged row tail, partial last column chunk, bias+ELU, residual
+                                               # tile kernels at a few thousand rows (these were row-streaming shapes while its threshold was 2048 rows;
+                                               # linear_rs_try takes M >= 16384 now -- that kernel is tested in test_gemm_gpu.py::test_row_streaming):
+                                               # fwd [K,N] and dgrad [N,K] forms, ragged M, N % 64 != 0, bias+ELU, residual
                                                (2100, 96, 288, 0, True), (4133, 384, 96, 2, False), (2048, 192, 136, 0, False),
                                                (2050, 288, 96, 0, True), (2304, 128, 384, 2, False)])
 def test_linear(dt, M, K, N, act, use_res):
