@@ -10,4 +10,5 @@ from .loss import (OGMFlow_loss, WaypointGrids, OccupancyFlowTaskConfig,     # n
 from .optim import Nadam                # noqa: F401
 from .metrics import compute_occupancy_flow_metrics, apply_sigmoid_to_occupancy_logits, OccupancyFlowMetrics     # noqa: F401
 from .submission import (QuantizedWaypoints, ResultDrain, quantize_waypoints, quantize_reference,     # noqa: F401
-                         compress_batch, compression_pool)
+                         compress_batch, compression_pool, CompressedWaypoints, compress_waypoints, compress_reference,
+                         DEFLATE_SEGMENT)

@@ -104,6 +104,8 @@ SIGNATURES = {
     'stj_outconv_pair_gather': [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp],
     'stj_outconv_pair_gather_q': [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp],
     'stj_quantize_waypoints': [vp, vp, ci, ci, ci, ci, vp],
+    'stj_compress_sizes': [ci, ci, ci, ci, vp, vp],
+    'stj_compress_waypoints': [vp, vp, vp, vp, ci, ci, ci, ci, vp],
     'stj_outconv_fwd': [vp, vp, vp, vp, ci, ci, ci, ci, ci, cl, cl, cl, ci, vp],
     'stj_outconv_bwd': [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cl, cl, cl, ci, vp, cl, ci, vp],
     'stj_outconv_bwd_workspace_bytes': [],

@@ -1,0 +1,311 @@
+// The challenge-format planes (quantize.hip's Q) as zlib streams, on the device: one stream per (scene, waypoint, field) plane, a
+// run-length DEFLATE with the fixed Huffman code (the format: strajnet_amd/submission.py, compress_reference; the per-byte rules:
+// deflate.h).  The reader of the challenge format only calls zlib.decompress, so any valid stream conforms; these are larger than zlib's
+// own and cost no host work.
+//
+//   deflate_encode_kernel   one workgroup per (plane, segment of DF_SEG bytes): the segment's DEFLATE block(s) into its slot of the
+//                           workspace, its byte count and its Adler-32 partials into the segment table
+//   deflate_offsets_kernel  one workgroup: per plane the scan of its segments' byte counts and its Adler-32, the scan of the planes'
+//                           totals -> `offsets`, and every stream's header and trailer
+//   deflate_pack_kernel     one workgroup per (plane, segment): the slot's bytes to their place in the packed buffer
+//
+// Workspace: [ segment table, 4 uint32 per segment: bytes, byte sum, weighted byte sum, offset in its stream | slots of DF_SLOT bytes ];
+// segments in the order of Q's memory (scene; 8 obs, 8 occ planes of nso segments each, 8 flow planes of nsf).  Streams in the order
+// scene, waypoint, (obs, occ, flow).
+#include "common.h"
+#include "deflate.h"
+
+static_assert(DF_SEG >= 4096 && DF_SEG <= 16384 && (DF_SEG & (DF_SEG - 1)) == 0, "DF_SEG: a power of two, 64 KB of static LDS at most");
+constexpr int DF_NW = DF_NT / 64;          // waves per workgroup
+
+// A workgroup's segment: where it lies in Q, its length and match distance, the plane's place in the stream order.
+struct DfSeg { long long src; int len, d, seg, final_, stream; };
+__device__ __forceinline__ DfSeg df_locate(long long g, int HW, int nso, int nsf) {
+  const int sps = 16 * nso + 8 * nsf;
+  const long long b = g / sps;
+  const int j = (int)(g % sps);
+  int mp, seg, n;
+  DfSeg r;
+  if (j < 16 * nso) { mp = j / nso; seg = j % nso; n = HW; r.d = 1; r.src = (long long)mp * HW; r.stream = (mp & 7) * 3 + (mp >> 3); }
+  else { const int jj = j - 16 * nso; mp = jj / nsf; seg = jj % nsf; n = 2 * HW; r.d = 2; r.src = 16ll * HW + (long long)mp * 2 * HW; r.stream = mp * 3 + 2; }
+  r.src += b * 32 * HW + (long long)seg * DF_SEG;
+  r.len = min(DF_SEG, n - seg * DF_SEG);
+  r.seg = seg;
+  r.final_ = seg * DF_SEG + r.len == n;
+  r.stream += (int)b * 24;
+  return r;
+}
+
+__global__ __launch_bounds__(DF_NT) void deflate_encode_kernel(const uint8_t* __restrict__ Q, uint8_t* __restrict__ slots, uint32_t* __restrict__ table,
+                                                               int HW, int nso, int nsf) {
+  __shared__ __attribute__((aligned(16))) uint32_t inw[4 + DF_SEG / 4];         // 16 bytes of history, then the segment
+  __shared__ __attribute__((aligned(16))) uint32_t bb[DF_SLOT / 4 + 4];         // the segment's output, built by OR into zeroed words
+  __shared__ int sc[5][DF_NW];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const DfSeg s = df_locate(blockIdx.x, HW, nso, nsf);
+  const int len = s.len, d = s.d;
+  const uint4* src4 = reinterpret_cast<const uint4*>(Q + s.src);
+  uint4* in4 = reinterpret_cast<uint4*>(inw);
+  for (int v = tid; v < len / 16; v += DF_NT) in4[1 + v] = src4[v];
+  if (tid == 0) in4[0] = s.seg ? src4[-1] : make_uint4(0, 0, 0, 0);               // history: the same plane's previous segment only
+  __syncthreads();
+
+  // this thread's run of 32 bytes (len is a multiple of 16: a run is whole, half, or empty)
+  const int base = tid * DF_RUN, cnt = max(0, min(DF_RUN, len - base));
+  uint32_t w[8];
+  {
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    const uint4 a = cnt > 0 ? in4[1 + 2 * tid] : z, b = cnt > 16 ? in4[2 + 2 * tid] : z;
+    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
+  }
+  uint32_t mask = cnt > 0 ? df_match_mask(w, inw[3 + 8 * tid], d) : 0u;
+  mask &= cnt == DF_RUN ? ~0u : (1u << cnt) - 1u;
+  if (s.seg == 0 && tid == 0) mask &= ~((1u << d) - 1u);                           // no history in front of the plane
+  const uint32_t nm = ~mask;
+
+  // P: the last non-matchable byte in front of this run; N: the first one behind it (workgroup exclusive max-scan / reverse min-scan)
+  int P, N;
+  {
+    int a = nm ? base + 31 - __builtin_clz(nm) : -1, b = nm ? base + __builtin_ctz(nm) : DF_SEG;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int ya = __shfl_up(a, o), yb = __shfl_down(b, o);
+      if (lane >= o) a = max(a, ya);
+      if (lane + o < 64) b = min(b, yb);
+    }
+    if (lane == 63) sc[0][wv] = a;
+    if (lane == 0) sc[1][wv] = b;
+    P = __shfl_up(a, 1); N = __shfl_down(b, 1);
+    if (lane == 0) P = -1;
+    if (lane == 63) N = DF_SEG;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < DF_NW; ++k) {
+      if (k < wv) P = max(P, sc[0][k]);
+      if (k > wv) N = min(N, sc[1][k]);
+    }
+  }
+
+  // bits of this run's tokens; the Adler-32 partials: sum of bytes, and sum of (len - i) * byte (what the bytes add to the running
+  // sum-of-sums by the segment's end), each reduced mod 65521 before 32 bits can overflow (a run: 32 * 255 * 16384 at most)
+  int tb = 0;
+  uint32_t s1 = 0, s2 = 0;
+#pragma unroll
+  for (int e = 0; e < DF_RUN; ++e) {
+    if (e >= cnt) continue;
+    const uint32_t byte = (w[e >> 2] >> (8 * (e & 3))) & 0xffu;
+    int nb;
+    df_token(nm, e, base, P, N, byte, d, &nb);
+    tb += nb;
+    s1 += byte;
+    s2 += (uint32_t)(len - base - e) * byte;
+  }
+  s2 %= DF_ADLER;
+  int off = tb, total;
+  {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int y = __shfl_up(off, o);
+      if (lane >= o) off += y;
+      s1 += __shfl_xor(s1, o);
+      s2 += __shfl_xor(s2, o);
+    }
+    if (lane == 63) { sc[2][wv] = off; sc[3][wv] = (int)(s1 % DF_ADLER); sc[4][wv] = (int)(s2 % DF_ADLER); }
+    __syncthreads();
+    off -= tb;
+    total = 0;
+    uint32_t t1 = 0, t2 = 0;
+#pragma unroll
+    for (int k = 0; k < DF_NW; ++k) {
+      if (k < wv) off += sc[2][k];
+      total += sc[2][k];
+      t1 += (uint32_t)sc[3][k];
+      t2 += (uint32_t)sc[4][k];
+    }
+    s1 = t1 % DF_ADLER;
+    s2 = t2 % DF_ADLER;
+  }
+
+  // fixed block: 3 header bits, the tokens, EOB (7 zero bits); a non-final one + the empty stored block 000, pad, 00 00 FF FF
+  const int fixed_bits = 3 + total + 7 + (s.final_ ? 0 : 3);
+  const int fixed_bytes = (fixed_bits + 7) / 8 + (s.final_ ? 0 : 4);
+  const bool stored = fixed_bytes > 5 + len;
+  const int out_bytes = stored ? 5 + len : fixed_bytes;
+  const int out_vecs = (out_bytes + 15) / 16;                 // <= DF_SLOT / 16
+  if (!stored) {
+    for (int i = tid; i < out_vecs * 4 + 2; i += DF_NT) bb[i] = 0;
+    __syncthreads();
+    if (tid == 0) {
+      atomicOr(&bb[0], (uint32_t)s.final_ | 2u);
+      if (!s.final_) {                                        // FF FF: the last two bytes
+        const int p = 8 * (fixed_bytes - 2);
+        atomicOr(&bb[p >> 5], 0xffffu << (p & 31));
+        if ((p & 31) > 16) atomicOr(&bb[(p >> 5) + 1], 0xffffu >> (32 - (p & 31)));
+      }
+    }
+    int wi = (3 + off) >> 5, fill = (3 + off) & 31;
+    unsigned long long acc = 0;
+#pragma unroll
+    for (int e = 0; e < DF_RUN; ++e) {
+      if (e >= cnt) continue;
+      const uint32_t byte = (w[e >> 2] >> (8 * (e & 3))) & 0xffu;
+      int nb;
+      const uint32_t v = df_token(nm, e, base, P, N, byte, d, &nb);
+      acc |= (unsigned long long)v << fill;
+      fill += nb;
+      if (fill >= 32) { atomicOr(&bb[wi], (uint32_t)acc); acc >>= 32; fill -= 32; ++wi; }
+    }
+    if (fill > 0 && acc) atomicOr(&bb[wi], (uint32_t)acc);
+  } else {
+    // stored block: BFINAL (BTYPE 00, padding), LEN, ~LEN, the raw bytes -- the segment shifted by 5 bytes
+    const uint32_t* x = inw + 4;
+    const uint32_t h4 = ((uint32_t)~len >> 8) & 0xffu;
+    for (int m = tid; m < out_vecs * 4; m += DF_NT) {
+      uint32_t v;
+      if (m == 0) v = (uint32_t)s.final_ | ((uint32_t)len & 0xffffu) << 8 | ((uint32_t)~len & 0xffu) << 24;
+      else {
+        const uint32_t lo = m == 1 ? h4 : m - 2 < len / 4 ? x[m - 2] >> 24 : 0u, hi = m - 1 < len / 4 ? x[m - 1] : 0u;
+        v = lo | hi << 8;
+      }
+      bb[m] = v;
+    }
+  }
+  __syncthreads();
+  uint4* slot4 = reinterpret_cast<uint4*>(slots + (long long)blockIdx.x * DF_SLOT);
+  const uint4* bb4 = reinterpret_cast<const uint4*>(bb);
+  for (int v = tid; v < out_vecs; v += DF_NT) slot4[v] = bb4[v];
+  if (tid == 0) {
+    uint32_t* t = table + 4ll * blockIdx.x;
+    t[0] = (uint32_t)out_bytes; t[1] = s1; t[2] = s2;
+  }
+}
+
+// One workgroup of 1024: thread <-> stream, in chunks of 1024 streams with a running carry.
+__global__ __launch_bounds__(1024) void deflate_offsets_kernel(uint32_t* __restrict__ table, uint8_t* __restrict__ out, uint32_t* __restrict__ offsets,
+                                                               int P, int HW, int nso, int nsf) {
+  __shared__ uint32_t ws[16];
+  __shared__ uint32_t carry;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int sps = 16 * nso + 8 * nsf;
+  if (tid == 0) carry = 0;
+  __syncthreads();
+  for (int p0 = 0; p0 < P; p0 += 1024) {
+    const int p = p0 + tid;
+    uint32_t total = 0, adler = 1;
+    if (p < P) {
+      const int b = p / 24, k = (p % 24) / 3, f = p % 3;
+      const int ns = f < 2 ? nso : nsf, n = f < 2 ? HW : 2 * HW;
+      uint32_t* t = table + 4 * ((long long)b * sps + (f < 2 ? (f * 8 + k) * nso : 16 * nso + k * nsf));
+      uint32_t A = 1, Bs = 0, acc = 2;
+      for (int s = 0; s < ns; ++s) {
+        const uint32_t L = (uint32_t)min(DF_SEG, n - s * DF_SEG);
+        t[4 * s + 3] = acc;
+        acc += t[4 * s];
+        Bs = (Bs + L * A + t[4 * s + 2]) % DF_ADLER;          // L * A < 2^14 * 2^16
+        A = (A + t[4 * s + 1]) % DF_ADLER;
+      }
+      total = acc + 4;
+      adler = Bs << 16 | A;
+    }
+    uint32_t inc = total;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t y = __shfl_up(inc, o);
+      if (lane >= o) inc += y;
+    }
+    if (lane == 63) ws[wv] = inc;
+    __syncthreads();
+    uint32_t off = carry + inc - total;
+    for (int k = 0; k < wv; ++k) off += ws[k];
+    if (p < P) {
+      offsets[p] = off;
+      out[off] = 0x78; out[off + 1] = 0x01;
+      uint8_t* tr = out + off + total - 4;
+      tr[0] = adler >> 24; tr[1] = adler >> 16; tr[2] = adler >> 8; tr[3] = adler;
+    }
+    __syncthreads();
+    if (tid == 1023) carry = off + total;
+    __syncthreads();
+  }
+  if (tid == 0) offsets[P] = carry;
+}
+
+// The slot's bytes to out + offsets[stream] + (offset in the stream): whole aligned 16-byte vectors of the destination are composed from
+// the slot's dwords (a funnel shift by the destination's misalignment); the destination's first and last partial vectors go bytewise.
+__global__ __launch_bounds__(256) void deflate_pack_kernel(const uint8_t* __restrict__ slots, const uint32_t* __restrict__ table,
+                                                           const uint32_t* __restrict__ offsets, uint8_t* __restrict__ out, int HW, int nso, int nsf) {
+  __shared__ __attribute__((aligned(16))) uint32_t lw[DF_SLOT / 4 + 8];
+  const int tid = threadIdx.x;
+  const DfSeg s = df_locate(blockIdx.x, HW, nso, nsf);
+  const uint32_t* t = table + 4ll * blockIdx.x;
+  const int bytes = (int)t[0];
+  const unsigned long long dst = (unsigned long long)offsets[s.stream] + t[3];
+  const int nv = (bytes + 15) / 16;
+  const uint4* slot4 = reinterpret_cast<const uint4*>(slots + (long long)blockIdx.x * DF_SLOT);
+  uint4* lw4 = reinterpret_cast<uint4*>(lw);
+  for (int v = tid; v <= nv; v += 256) lw4[v] = v < nv ? slot4[v] : make_uint4(0, 0, 0, 0);
+  __syncthreads();
+  const int a = (int)(dst & 15);
+  uint8_t* dsta = out + (dst - a);                       // 16-byte aligned; destination byte 16 c + i is slot byte 16 c + i - a
+  const int nch = (a + bytes + 15) / 16;
+  const uint8_t* lb = reinterpret_cast<const uint8_t*>(lw);
+  for (int c = tid; c < nch; c += 256) {
+    const int j0 = 16 * c - a;
+    if (j0 >= 0 && j0 + 16 <= bytes) {
+      const int jd = j0 >> 2, sh = (j0 & 3) * 8;
+      uint32_t v[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = sh ? lw[jd + q] >> sh | lw[jd + q + 1] << (32 - sh) : lw[jd + q];
+      *reinterpret_cast<uint4*>(dsta + 16 * c) = make_uint4(v[0], v[1], v[2], v[3]);
+    } else {
+      for (int i = 0; i < 16; ++i)
+        if (j0 + i >= 0 && j0 + i < bytes) dsta[16 * c + i] = lb[j0 + i];
+    }
+  }
+}
+
+static int df_shape(const char* who, int B, int Tn, int Hh, int Ww, long long* nseg, long long* cap, int* nso, int* nsf) {
+  if (B <= 0 || Hh <= 0 || Ww <= 0) { stj_set_error("%s: empty problem", who); return STJ_EINVAL; }
+  const long long HW = (long long)Hh * Ww;
+  if (Tn != 8 || HW % 256 || HW > (1 << 28)) {
+    stj_set_error("%s: Tn = 8, H * W a multiple of 256 only (Tn %d, H %d, W %d)", who, Tn, Hh, Ww);
+    return STJ_EUNSUPPORTED;
+  }
+  *nso = (int)((HW + DF_SEG - 1) / DF_SEG);
+  *nsf = (int)((2 * HW + DF_SEG - 1) / DF_SEG);
+  *nseg = (long long)B * (16 * *nso + 8 * *nsf);
+  *cap = (long long)B * (32 * HW + 5ll * (16 * *nso + 8 * *nsf) + 6 * 24);            // n + 5 ceil(n / DF_SEG) + 6 per stream
+  if (*nseg > 0x7fffffffLL || *cap > 0xffffffffLL) {
+    stj_set_error("%s: batch too large for 32-bit stream offsets (B %d, H %d, W %d)", who, B, Hh, Ww);
+    return STJ_EUNSUPPORTED;
+  }
+  return STJ_OK;
+}
+static inline long long df_table_bytes(long long nseg) { return (nseg * 16 + 255) / 256 * 256; }
+
+extern "C" int stj_compress_sizes(int B, int Tn, int H, int W, long long* work_bytes, long long* out_capacity) {
+  long long nseg, cap; int nso, nsf;
+  const int rc = df_shape("stj_compress_sizes", B, Tn, H, W, &nseg, &cap, &nso, &nsf);
+  if (rc != STJ_OK) return rc;
+  *work_bytes = df_table_bytes(nseg) + nseg * DF_SLOT;
+  *out_capacity = (cap + 15) / 16 * 16;
+  return STJ_OK;
+}
+
+extern "C" int stj_compress_waypoints(const uint8_t* Q, void* work, uint8_t* out, uint32_t* offsets, int B, int Tn, int H, int W, hipStream_t stream) {
+  long long nseg, cap; int nso, nsf;
+  const int rc = df_shape("stj_compress_waypoints", B, Tn, H, W, &nseg, &cap, &nso, &nsf);
+  if (rc != STJ_OK) return rc;
+  if (((uintptr_t)Q | (uintptr_t)work | (uintptr_t)out | (uintptr_t)offsets) & 15) {
+    stj_set_error("stj_compress_waypoints: 16-byte aligned buffers only");
+    return STJ_EUNSUPPORTED;
+  }
+  uint32_t* table = reinterpret_cast<uint32_t*>(work);
+  uint8_t* slots = reinterpret_cast<uint8_t*>(work) + df_table_bytes(nseg);
+  const int HW = H * W;
+  hipLaunchKernelGGL(deflate_encode_kernel, dim3((unsigned)nseg), dim3(DF_NT), 0, stream, Q, slots, table, HW, nso, nsf);
+  hipLaunchKernelGGL(deflate_offsets_kernel, dim3(1), dim3(1024), 0, stream, table, out, offsets, B * 24, HW, nso, nsf);
+  hipLaunchKernelGGL(deflate_pack_kernel, dim3((unsigned)nseg), dim3(256), 0, stream, (const uint8_t*)slots, (const uint32_t*)table,
+                     (const uint32_t*)offsets, out, HW, nso, nsf);
+  return stj_check_launch("stj_compress_waypoints");
+}

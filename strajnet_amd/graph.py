@@ -104,6 +104,8 @@ class GraphedForward:
 
     quantized=True: the captured forward is model.predict_quantized and the result a submission.QuantizedWaypoints over static memory
     (the challenge format's bytes: 4 per cell and waypoint instead of 16 to bring to the host; submission.ResultDrain does that).
+    With compressed=True as well the captured forward is model.predict_compressed and the result a submission.CompressedWaypoints over
+    static memory: the zlib strings, of which ResultDrain brings only the bytes they really have.
 
     pipeline_agents=True: the agent branch (trajNet: ~30 dependent launches of a few microseconds that a replayed graph starts only when
     the raster encoder is through -- 0.3 of the 6.3 ms B = 32 step with nothing beside them, profiles/r05_c_timeline_infer_b32_f16.txt) is
@@ -114,9 +116,12 @@ class GraphedForward:
     measured 1.3 % SLOWER in three same-box pairs, 5333 / 5118 / 5333 vs 5390 / 5206 / 5412 scenes/s: where those launches sit decides when the
     executor starts the other branches, DESIGN 4e.  Not kept.)"""
 
-    def __init__(self, model, batch, warmup=2, pipeline_agents=False, quantized=False):
+    def __init__(self, model, batch, warmup=2, pipeline_agents=False, quantized=False, compressed=False):
+        if compressed and not quantized:
+            raise ValueError('GraphedForward: compressed=True compresses the quantised output: pass quantized=True with it')
         self.model = model
         self.quantized = quantized
+        self.compressed = compressed
         self.static = {k: v.clone() for k, v in batch.items() if k in ('ogm', 'map_img', 'obs', 'occ', 'flow')}
         self.pipeline_agents = pipeline_agents
         self._prefetched = False
@@ -153,6 +158,8 @@ class GraphedForward:
 
     def _eager(self):
         x = self.static
+        if self.compressed:
+            return self.model.predict_compressed(x['ogm'], x['map_img'], obs=x['obs'], occ=x['occ'], mapt=None, flow=x['flow'])
         if self.quantized:
             return self.model.predict_quantized(x['ogm'], x['map_img'], obs=x['obs'], occ=x['occ'], mapt=None, flow=x['flow'])
         return self.model(x['ogm'], x['map_img'], training=False, obs=x['obs'], occ=x['occ'], mapt=None, flow=x['flow'])

@@ -848,6 +848,12 @@ class STrajNet:
                 return QuantizedWaypoints(out, H, H)
             return quantize_waypoints(out)
 
+    def predict_compressed(self, ogm, map_img, obs=None, occ=None, mapt=None, flow=None, out=None):
+        """predict_quantized followed by submission.compress_waypoints: the result as the challenge format's zlib strings, compressed on
+        the device (submission.CompressedWaypoints; `out`: one to write into)."""
+        from .submission import compress_waypoints
+        return compress_waypoints(self.predict_quantized(ogm, map_img, obs=obs, occ=occ, mapt=mapt, flow=flow), out=out)
+
     def call(self, ogm, map_img, training=True, obs=None, occ=None, mapt=None, flow=None, dense_vec=None, dense_map=None):
         """STrajNet.call (modules.py:815-839).  mapt is ignored (actor_only=True), as in the reference."""
         if obs is None or occ is None or flow is None:

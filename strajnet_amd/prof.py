@@ -96,6 +96,14 @@ def _quantize(a):
     return f'quantize_waypoints[{H}x{W},B{B}]', 'quantize', 0.0, 0.0, 20 * Tn * B * H * W
 
 
+def _compress(a):
+    """stj_compress_waypoints(Q, work, out, offsets, B, Tn, H, W, stream): the 4 Tn bytes per cell read once + the streams written.  The
+    streams' size depends on the data and is not known to the host without a synchronisation: counted at its bound, the input's size
+    (what noise-like planes give; planes of runs write a small fraction of it)."""
+    B, Tn, H, W = a[4], a[5], a[6], a[7]
+    return f'compress_waypoints[{H}x{W},B{B}]', 'compress', 0.0, 0.0, 8 * Tn * B * H * W
+
+
 def _upconv_res(a):
     F, Hi, Wi, Cin, Cout, dt = a[7], a[8], a[9], a[10], a[11], a[12]
     es = _es(dt)
@@ -200,7 +208,7 @@ def _ln_chain(a):
 MODELS = {
     'stj_gemm': _gemm,
     'stj_patch_embed_fwd': _patch_embed, 'stj_layernorm_bwd_chain': _ln_chain,
-    'stj_upconv_fwd': _upconv('fwd'), 'stj_upconv_fwd_head': _upconv_head, 'stj_outconv_pair_gather': _pair_gather, 'stj_outconv_pair_gather_q': _pair_gather_q, 'stj_quantize_waypoints': _quantize, 'stj_upconv_fwd_res': _upconv_res, 'stj_elu_res_bwd': _elu_res, 'stj_upconv_dgrad': _upconv('dgrad'), 'stj_upconv_wgrad': _upconv('wgrad'),
+    'stj_upconv_fwd': _upconv('fwd'), 'stj_upconv_fwd_head': _upconv_head, 'stj_outconv_pair_gather': _pair_gather, 'stj_outconv_pair_gather_q': _pair_gather_q, 'stj_quantize_waypoints': _quantize, 'stj_compress_waypoints': _compress, 'stj_upconv_fwd_res': _upconv_res, 'stj_elu_res_bwd': _elu_res, 'stj_upconv_dgrad': _upconv('dgrad'), 'stj_upconv_wgrad': _upconv('wgrad'),
     'stj_outconv_fwd': _outconv('fwd'), 'stj_outconv_pair_fwd': _outconv_pair, 'stj_outconv_bwd': _outconv('bwd'),
     'stj_layernorm_fwd': _ln('fwd'), 'stj_layernorm_bwd': _ln('bwd'), 'stj_layernorm_res_fwd': _ln('res_fwd'),
     'stj_win_attn_fwd': _win('fwd'), 'stj_win_attn_bwd': _win('bwd'),

@@ -8,10 +8,14 @@
 The quantisation runs on the device, in front of the device-to-host copy (4 bytes per cell and waypoint instead of 16): as a kernel of
 its own behind any float32 output (stj_quantize_waypoints) or, on the 16-bit inference path, in the epilogue of the kernel that produces
 the logits (stj_outconv_pair_gather_q; STrajNet.predict_quantized picks).  ResultDrain brings the bytes to pinned host memory beside the
-replaying thread; compression is host work (zlib) on the caller's side.  `quantize_reference` is the only CPU code path here.
+replaying thread.  Compression: either host work (zlib: QuantizedWaypoints.compressed / compress_batch, zlib's own sizes) or on the
+device (compress_waypoints, stj_compress_waypoints: one zlib stream per plane, run-length DEFLATE with the fixed Huffman code in the
+format `compress_reference` states; larger streams, no host work, and only the streams cross to the host).  `quantize_reference` and
+`compress_reference` are the only CPU code paths here.
 
 dequantize() loses at most 1/510 in probability and 0.5 per flow component (flow beyond [-128, 127] is clipped, as in the format).
 """
+import ctypes
 import os
 import threading
 import zlib
@@ -20,9 +24,11 @@ import numpy as np
 import torch
 
 from .loss import WaypointGrids
+from ._lib import call as _host_call
 from .ops import _p, _st, call
 
 NUM_WAYPOINTS = 8
+DEFLATE_SEGMENT = 8192      # bytes of a plane per DEFLATE block (csrc/deflate.hip: DF_SEG); a power of two in 4096..32768
 
 
 def quantize_reference(out):
@@ -131,9 +137,168 @@ def compress_batch(qw, pool):
     return list(pool.map(qw.compressed, range(qw.batch)))
 
 
+# ---------------------------------------------------------------------------------------------------- device-side compression
+# The stream of one plane x of n bytes at match distance d (1: occupancy, 2: flow, so that equal consecutive (dx, dy) pairs match):
+#   78 01 | one DEFLATE block per segment of DEFLATE_SEGMENT bytes | Adler-32(x), big-endian
+# Byte i of the PLANE is matchable if i >= d and x[i] == x[i - d] (history reaches into the previous segment, never in front of the
+# plane).  Within a segment, a maximal stretch of L matchable bytes becomes matches of min(258, rest) at distance d while rest >= 3; the
+# 1-2 bytes left over, and stretches shorter than 3, are literals.  Fixed Huffman code (BTYPE 01).  A non-final fixed block is followed
+# by an empty stored block (bits 000, pad, 00 00 FF FF), so every segment is a whole number of bytes; the final one pads to the byte.
+# A segment whose fixed form, flush included, exceeds 5 + len bytes is a stored block (BTYPE 00) instead.  Hence a stream has at most
+# n + 5 ceil(n / DEFLATE_SEGMENT) + 6 bytes.
+
+def _rev(v, bits):
+    return int(format(v, f'0{bits}b')[::-1], 2)
+
+
+def _fixed_tables():
+    """(literal value, literal bits) per byte, and per match length 3..258 the (value, bits) of length code + extra bits -- RFC 1951
+    3.2.5 / 3.2.6; Huffman codes go out most significant bit first, i.e. reversed in the LSB-first bit stream, extra bits as they are."""
+    lit_v = np.array([_rev(0x30 + v, 8) if v < 144 else _rev(0x190 + v - 144, 9) for v in range(256)], np.uint64)
+    lit_n = np.array([8 if v < 144 else 9 for v in range(256)], np.int64)
+    base = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
+    extra = [0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0]
+    len_v, len_n = {}, {}
+    for m in range(3, 259):
+        c = max(i for i in range(29) if base[i] <= m and (i == 28 or m < 258))
+        sym = 257 + c
+        hv, hn = (_rev(sym - 256, 7), 7) if sym < 280 else (_rev(0xC0 + sym - 280, 8), 8)
+        len_v[m], len_n[m] = hv | ((m - base[c]) << hn), hn + extra[c]
+    return lit_v, lit_n, len_v, len_n
+
+
+_LIT_V, _LIT_N, _LEN_V, _LEN_N = _fixed_tables()
+
+
+def _pack_bits(vals, nbits, total_bits):
+    """Tokens (value, bit count <= 25) laid end to end, least significant bit first -> ceil(total_bits / 8) bytes."""
+    out = np.zeros((total_bits + 7) // 8 + 4, np.uint8)
+    off = np.concatenate([[0], np.cumsum(nbits)[:-1]]).astype(np.int64)
+    sh = vals << (off & 7).astype(np.uint64)
+    for k in range(4):
+        np.bitwise_or.at(out, (off >> 3) + k, ((sh >> np.uint64(8 * k)) & np.uint64(0xff)).astype(np.uint8))
+    return out[:(total_bits + 7) // 8]
+
+
+def compress_reference(plane_bytes, d):
+    """The zlib stream stj_compress_waypoints writes for one plane (`plane_bytes`: bytes or a uint8 array; d = 1 for an occupancy plane,
+    2 for a flow plane), byte for byte.  CPU; the statement of the format, for tests and for users without a GPU at hand."""
+    x = np.frombuffer(bytes(plane_bytes), np.uint8) if not isinstance(plane_bytes, np.ndarray) else plane_bytes.reshape(-1).view(np.uint8)
+    n, S = x.size, DEFLATE_SEGMENT
+    if n == 0 or d not in (1, 2):
+        raise ValueError('compress_reference: a non-empty plane and d in (1, 2)')
+    matchable = np.zeros(n, bool)
+    matchable[d:] = x[d:] == x[:-d]
+    dist_v = _rev(d - 1, 5)
+    out = [b'\x78\x01']
+    for s0 in range(0, n, S):
+        seg, m = x[s0:s0 + S], matchable[s0:s0 + S]
+        L, final = seg.size, s0 + S >= n
+        vals, nbits = _LIT_V[seg].copy(), _LIT_N[seg].copy()
+        edge = np.flatnonzero(np.diff(np.concatenate([[False], m, [False]]).astype(np.int8)))
+        for a, e in zip(edge[0::2], edge[1::2]):                   # the stretches [a, e) of matchable bytes
+            pos, rest = int(a), int(e - a)
+            while rest >= 3:
+                ml = min(258, rest)
+                vals[pos] = _LEN_V[ml] | (dist_v << _LEN_N[ml])
+                nbits[pos] = _LEN_N[ml] + 5
+                nbits[pos + 1:pos + ml] = 0
+                pos, rest = pos + ml, rest - ml
+        keep = nbits > 0
+        vals = np.concatenate([[np.uint64(int(final) | 2)], vals[keep]]).astype(np.uint64)          # BFINAL, BTYPE 01 in front; EOB = 7 zero bits
+        nbits = np.concatenate([[3], nbits[keep]])
+        bits = int(nbits.sum()) + 7 + (0 if final else 3)                                         # non-final: + the empty stored block's 000
+        fixed = _pack_bits(vals, nbits, bits).tobytes() + (b'' if final else b'\x00\x00\xff\xff')
+        if len(fixed) > 5 + L:
+            out.append(bytes([int(final), L & 255, L >> 8, ~L & 255, (~L >> 8) & 255]) + seg.tobytes())
+        else:
+            out.append(fixed)
+    out.append(zlib.adler32(x.tobytes()).to_bytes(4, 'big'))
+    return b''.join(out)
+
+
+def compress_sizes(B, H, W, Tn=NUM_WAYPOINTS):
+    """(workspace bytes, capacity of the packed buffer) of stj_compress_waypoints; raises StjError for a shape it does not take."""
+    work, cap = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    _host_call('stj_compress_sizes', B, Tn, H, W, ctypes.c_void_p(ctypes.addressof(work)), ctypes.c_void_p(ctypes.addressof(cap)))
+    return work.value, cap.value
+
+
+class CompressedWaypoints:
+    """The zlib streams of a batch, packed: `buf` uint8 (device or host), `offsets` [B*Tn*3 + 1] (int32 storage, read as uint32): stream
+    s = (b*Tn + k)*3 + i, i in (obs, occ, flow), is buf[offsets[s]:offsets[s + 1]] -- the order of QuantizedWaypoints.compressed(b)[k][i],
+    so a scene's 3 Tn streams are one contiguous slice.  On the device `buf` has the capacity of the worst case and only the first
+    offsets[-1] bytes mean anything; `work` is the kernels' scratch (kept so that the object can be written again: compress_waypoints(out=))."""
+
+    def __init__(self, buf, offsets, B, Tn=NUM_WAYPOINTS, work=None):
+        if buf.dtype != torch.uint8 or buf.dim() != 1 or offsets.dim() != 1 or offsets.numel() != 3 * B * Tn + 1 or offsets.dtype != torch.int32:
+            raise ValueError(f'CompressedWaypoints: expected a uint8 [n] buffer and int32 [{3 * B * Tn + 1}] offsets, got '
+                             f'{buf.dtype} {tuple(buf.shape)}, {offsets.dtype} {tuple(offsets.shape)}')
+        self.buf, self.offsets, self.B, self.Tn, self.work = buf, offsets, B, Tn, work
+
+    @classmethod
+    def empty(cls, B, H, W, device, Tn=NUM_WAYPOINTS):
+        """Device memory for the streams of a [B, 4*Tn*H*W] QuantizedWaypoints."""
+        work, cap = compress_sizes(B, H, W, Tn)
+        return cls(torch.empty(cap, dtype=torch.uint8, device=device), torch.empty(3 * B * Tn + 1, dtype=torch.int32, device=device), B, Tn,
+                   work=torch.empty(work, dtype=torch.uint8, device=device))
+
+    @property
+    def batch(self):
+        return self.B
+
+    def _host_offsets(self):
+        return self.offsets.cpu().numpy().view(np.uint32).astype(np.int64)
+
+    @property
+    def nbytes(self):
+        """Total size of the streams (a device object is asked: one small synchronous copy)."""
+        return int(self._host_offsets()[-1])
+
+    def cpu(self):
+        """Synchronous copy to host memory: the offsets table, then the offsets[-1] bytes that are streams."""
+        if not self.buf.is_cuda:
+            return self
+        off = self.offsets.cpu()
+        total = int(off.numpy().view(np.uint32)[-1])
+        return CompressedWaypoints(self.buf[:total].cpu(), off, self.B, self.Tn)
+
+    def scene_bytes(self, b):
+        """The 3 Tn streams of scene b, back to back, as bytes."""
+        off = self._host_offsets()
+        lo, hi = int(off[3 * self.Tn * b]), int(off[3 * self.Tn * (b + 1)])
+        return self.buf[lo:hi].cpu().numpy().tobytes()
+
+    def streams(self, b):
+        """Scene b: a list of Tn (obs, occ, flow) zlib strings, the shape of QuantizedWaypoints.compressed(b)."""
+        off = self._host_offsets()[3 * self.Tn * b:3 * self.Tn * (b + 1) + 1]
+        raw = self.buf[int(off[0]):int(off[-1])].cpu().numpy().tobytes()
+        cut = [int(o - off[0]) for o in off]
+        return [tuple(raw[cut[3 * k + i]:cut[3 * k + i + 1]] for i in range(3)) for k in range(self.Tn)]
+
+
+def compress_waypoints(qw, out=None):
+    """A device QuantizedWaypoints -> CompressedWaypoints (stj_compress_waypoints: no host synchronisation, no allocation with `out`
+    given -- a CompressedWaypoints.empty of the same shape, written in place -- so the call can be captured in a graph)."""
+    if not qw.buf.is_cuda:
+        raise RuntimeError('compress_waypoints: CUDA (ROCm) buffers only: the HIP path has no CPU fallback (CPU: compress_reference, '
+                           'or zlib through QuantizedWaypoints.compressed)')
+    B = qw.batch
+    if out is None:
+        out = CompressedWaypoints.empty(B, qw.H, qw.W, qw.buf.device, qw.Tn)
+    else:
+        work, cap = compress_sizes(B, qw.H, qw.W, qw.Tn)
+        if (out.work is None or not out.buf.is_cuda or out.B != B or out.Tn != qw.Tn or out.buf.numel() < cap or out.work.numel() < work
+                or out.buf.device != qw.buf.device):
+            raise ValueError('compress_waypoints: `out` must be a CompressedWaypoints.empty() of the same shape on the same device')
+    call('stj_compress_waypoints', _p(qw.buf), _p(out.work), _p(out.buf), _p(out.offsets), B, qw.Tn, qw.H, qw.W, _st())
+    return out
+
+
 class ResultDrain:
     """The output-side twin of data.HostFeed: brings the static quantised buffer of a GraphedForward(quantized=True) to pinned host
-    memory, one batch per replay, without stalling the replaying thread:
+    memory, one batch per replay, without stalling the replaying thread (or the CompressedWaypoints of a GraphedForward(quantized=True,
+    compressed=True): then the worker brings the offsets table first and only the offsets[-1] bytes that are streams):
 
         drain = ResultDrain(gf.out)
         for batch in batches:
@@ -159,6 +324,11 @@ class ResultDrain:
         self.depth, self.chunk = int(depth), int(chunk_bytes)
         self.stage = [torch.empty_like(qw.buf) for _ in range(self.depth)]
         self.ring = [torch.empty(qw.buf.shape, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
+        self.compressed = isinstance(qw, CompressedWaypoints)
+        if self.compressed:       # + the offsets table; the worker reads it first and brings only offsets[-1] bytes of the buffer
+            self.stage_off = [torch.empty_like(qw.offsets) for _ in range(self.depth)]
+            self.ring_off = [torch.empty(qw.offsets.shape, dtype=torch.int32).pin_memory() for _ in range(self.depth)]
+            self._total = [0] * self.depth
         self.copy = _copy_stream(self.dev)
         self._done = [torch.cuda.Event() for _ in range(self.depth)]      # slot i's host copy has arrived
         self._ready = [torch.cuda.Event() for _ in range(self.depth)]     # slot i's staging buffer holds the batch
@@ -184,7 +354,12 @@ class ResultDrain:
                 with torch.cuda.stream(self.copy):
                     self.copy.wait_event(self._ready[slot])
                     s, d = self.stage[slot].view(-1), self.ring[slot].view(-1)
-                    for i in range(0, s.numel(), self.chunk):
+                    n = s.numel()
+                    if self.compressed:
+                        self.ring_off[slot].copy_(self.stage_off[slot], non_blocking=True)
+                        self.copy.synchronize()              # (this thread's own stream: the replaying thread is not held up)
+                        n = self._total[slot] = int(self.ring_off[slot].numpy().view(np.uint32)[-1])
+                    for i in range(0, n, self.chunk):
                         d[i:i + self.chunk].copy_(s[i:i + self.chunk], non_blocking=True)
                     self._done[slot].record(self.copy)
             except Exception as e:       # surfaced by the next take()
@@ -200,6 +375,8 @@ class ResultDrain:
         if self._n_sub >= self.depth:
             main.wait_event(self._done[slot])        # (taken already, so recorded: the slot's previous host copy has left the staging buffer)
         self.stage[slot].copy_(self.src.buf, non_blocking=True)
+        if self.compressed:
+            self.stage_off[slot].copy_(self.src.offsets, non_blocking=True)
         self._enq[slot].clear()
         self._ready[slot].record(main)
         self._n_sub += 1
@@ -208,7 +385,7 @@ class ResultDrain:
             self._cv.notify()
 
     def take(self):
-        """The oldest submitted batch as a host QuantizedWaypoints (a view of ring memory)."""
+        """The oldest submitted batch as a host QuantizedWaypoints (CompressedWaypoints for such a source), a view of ring memory."""
         if self._n_take >= self._n_sub:
             raise RuntimeError('ResultDrain: nothing submitted')
         slot = self._n_take % self.depth
@@ -218,6 +395,8 @@ class ResultDrain:
             raise e
         self._done[slot].synchronize()
         self._n_take += 1
+        if self.compressed:
+            return CompressedWaypoints(self.ring[slot][:self._total[slot]], self.ring_off[slot], self.src.B, self.src.Tn)
         return QuantizedWaypoints(self.ring[slot], self.src.H, self.src.W, self.src.Tn)
 
     def close(self):

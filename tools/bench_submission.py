@@ -2,11 +2,17 @@
 """What bringing the inference result to the host costs (config 4: B = 32 fp16, GraphedForward under replay, agent pipeline on).
 
   --mode rows   scenes/s for (a) no read-back (bench.py --infer's figure), (b) the float32 output copied to pinned memory each step,
-                (c) quantised output + ResultDrain, (d) as (c) plus zlib compression of every scene on 16 threads
+                (c) quantised output + ResultDrain, (d) as (c) plus zlib compression of every scene on 16 threads, (e) the graph that
+                also compresses on the device (GraphedForward(quantized=True, compressed=True)) + ResultDrain, no host zlib; bytes per
+                scene of (d) and (e) side by side
   --mode ab     GraphedForward(quantized=True) with the quantising gather (stj_outconv_pair_gather_q) against the same graph built from
                 stj_outconv_pair_gather + stj_quantize_waypoints, alternating, --pairs times; each build is timed TWICE in a row per
                 visit, so the spread of repeated runs of the same build is measured in the same call
   --mode trace  a few replays of both quantised graphs and nothing else: the workload of a `rocprofv3 --kernel-trace --stats` run
+  --sparse      (instead of a mode) random weights give noise-like planes, which the device-side compressor mostly stores; this fills a
+                static quantised buffer ONCE with synthetic sparse planes (seeded blobs on a zero background) and times
+                stj_compress_waypoints (captured) + ResultDrain alone against host compress_batch of the same bytes on --threads threads.
+                With --trace-only: a few replays of the captured compression and nothing else, for a kernel trace.
 
 Every timing is a host clock around `--steps` replays that end in a device synchronise, after `--warmup` replays, profiler off.
 One JSON line per mode on stdout."""
@@ -27,24 +33,125 @@ ap.add_argument('--pairs', type=int, default=3)
 ap.add_argument('--batch', type=int, default=32)
 ap.add_argument('--threads', type=int, default=16)
 ap.add_argument('--chunk-bytes', type=int, default=3 << 19)
+ap.add_argument('--sparse', action='store_true')
+ap.add_argument('--noise', action='store_true', help='with --sparse: uniformly random planes instead (the stored fallback everywhere)')
+ap.add_argument('--trace-only', action='store_true')
 a = ap.parse_args()
 
 import bench
-from strajnet_amd import STrajNet, ResultDrain, compress_batch, compression_pool
+from strajnet_amd import (STrajNet, ResultDrain, compress_batch, compression_pool, QuantizedWaypoints, CompressedWaypoints,
+                          compress_waypoints)
 from strajnet_amd.graph import GraphedForward
 
 assert torch.cuda.is_available(), 'bench_submission.py needs a GPU'
 dev = torch.device('cuda', 0)
 torch.cuda.set_device(dev)
 B = a.batch
+
+
+def sparse_planes(B, H, W, seed, noise=False):
+    """[B, 32*H*W] uint8 in QuantizedWaypoints' layout: per plane a zero background with a dozen rectangular blobs -- occupancy: a
+    plateau of one value with a one-cell rim of half of it; flow: one (dx, dy) per blob."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    if noise:
+        return torch.from_numpy(rng.integers(0, 256, (B, 32 * H * W), dtype=np.uint8))
+    buf = np.zeros((B, 24, 2 * H * W), np.uint8)
+    for b in range(B):
+        for p in range(24):
+            img = np.zeros((H, W, 2 if p >= 16 else 1), np.uint8)
+            for _ in range(12):
+                h, w = rng.integers(4, 28, 2)
+                y, x0 = rng.integers(0, H - h), rng.integers(0, W - w)
+                if p >= 16:
+                    img[y:y + h, x0:x0 + w] = rng.integers(0, 256, 2, dtype=np.uint8)
+                else:
+                    v = rng.integers(32, 256)
+                    img[y:y + h, x0:x0 + w] = v // 2
+                    img[y + 1:y + h - 1, x0 + 1:x0 + w - 1] = v
+            buf[b, p, :img.size] = img.reshape(-1)
+    n = H * W
+    out = np.concatenate([buf[:, :16, :n].reshape(B, -1), buf[:, 16:].reshape(B, -1)], axis=1)
+    return torch.from_numpy(np.ascontiguousarray(out))
+
+
+if a.sparse:
+    H = 256
+    host_q = QuantizedWaypoints(sparse_planes(B, H, H, 1234, a.noise), H, H)
+    qw = QuantizedWaypoints(host_q.buf.to(dev), H, H)
+    cw = CompressedWaypoints.empty(B, H, H, dev)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        compress_waypoints(qw, out=cw)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        compress_waypoints(qw, out=cw)
+    if a.trace_only:
+        for _ in range(10):
+            g.replay()
+        torch.cuda.synchronize()
+        print(json.dumps({'mode': 'sparse-trace', 'batch': B, 'replays': 10 + 1, 'noise': a.noise, 'input_bytes': qw.buf.numel(),
+                          'stream_bytes': cw.nbytes}), flush=True)
+        sys.exit(0)
+    drain = ResultDrain(cw, depth=3, chunk_bytes=a.chunk_bytes)
+    pending = [0]
+
+    def step():
+        g.replay()
+        drain.submit()
+        pending[0] += 1
+        if pending[0] > 1:
+            drain.take()
+            pending[0] -= 1
+
+    def finish():
+        while pending[0]:
+            drain.take()
+            pending[0] -= 1
+    for _ in range(a.warmup):
+        step()
+    finish()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(a.steps):
+        step()
+    finish()
+    torch.cuda.synchronize()
+    dev_rate = B * a.steps / (time.perf_counter() - t0)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(20):
+        g.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    drain.close()
+    pool = compression_pool(a.threads)
+    compress_batch(host_q, pool)
+    reps = max(1, min(5, a.steps))
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        comp = compress_batch(host_q, pool)
+    host_rate = B * reps / (time.perf_counter() - t0)
+    pool.shutdown()
+    zl = sum(len(s) for scene in comp for wp in scene for s in wp)
+    print(json.dumps({'mode': 'sparse', 'noise': a.noise, 'batch': B, 'steps': a.steps, 'warmup': a.warmup, 'threads': a.threads,
+                      'device_compress_drain_scenes_per_s': round(dev_rate, 1), 'host_zlib_scenes_per_s': round(host_rate, 1),
+                      'compress_ms_per_batch': round(e0.elapsed_time(e1) / 20, 4),
+                      'raw_bytes_per_scene': qw.buf.shape[1], 'device_stream_bytes_per_scene': cw.nbytes / B,
+                      'zlib_bytes_per_scene': zl / B}), flush=True)
+    sys.exit(0)
+
 model = STrajNet(bench.CFG256, fg_msa=True, fg=True, large_ogm=False, dtype=torch.float16, device=dev, seed=0)
 x = bench.synth_batch(B, 1234, dev, 256)
 
 
-def graph(quantized, fused=True):
+def graph(quantized, fused=True, compressed=False):
     model.fused_quantize = fused
     try:
-        return GraphedForward(model, x, pipeline_agents=True, quantized=quantized)
+        return GraphedForward(model, x, pipeline_agents=True, quantized=quantized, compressed=compressed)
     finally:
         model.fused_quantize = True
 
@@ -118,6 +225,29 @@ if a.mode == 'rows':
             pool.shutdown()
         drain.close()
     res['c_bytes_per_scene'] = gq.out.buf.shape[1]
+    del gq
+    ge = graph(True, compressed=True)
+    drain = ResultDrain(ge.out, depth=3, chunk_bytes=a.chunk_bytes)
+    pending, sizes = [0], []
+
+    def consume_e():
+        sizes.append(drain.take().buf.numel())
+        pending[0] -= 1
+
+    def step_e():
+        ge()
+        ge.prefetch_agents()
+        drain.submit()
+        pending[0] += 1
+        if pending[0] > 1:
+            consume_e()
+
+    def finish_e():
+        while pending[0]:
+            consume_e()
+    res['e_compressed_drain'] = timed(step_e, finish_e)
+    res['e_compressed_bytes_per_scene'] = sum(sizes) / len(sizes) / B
+    drain.close()
     print(json.dumps({'mode': 'rows', 'batch': B, 'steps': a.steps, 'warmup': a.warmup, 'unit': 'scenes/s',
                       **{k: round(v, 1) for k, v in res.items()}}), flush=True)
 elif a.mode == 'ab':
