@@ -480,6 +480,19 @@ int stj_loss_fwd_bwd(const float* logits, const float* gt_obs, const float* gt_o
 int stj_decode_raw(const void* src, int kind, float* dst, long long n_outer, int H, int W, int C, int y0, int x0, int Ho,
                    int Wo, float scale, hipStream_t stream);
 
+/* Packed record features expanded on the device (csrc/unpack.hip; the format is stated by pack_bits / pack_sparse / unpack_reference in
+ * strajnet_amd/data.py).  A scene's decoded array (after the reshape and centre crop, before the cast) is flattened to n elements.
+ * stj_unpack_bits: element i is bit i & 7 of byte i >> 3; dst f32 [n_total] = 1.0f / 0.0f (scenes back to back: n_total = B n).
+ * stj_unpack_sparse: per scene mask uint32 [n / 32] (same bit order), offs uint32 [ceil(n / 8192) + 1] (exclusive prefix of the present
+ * counts per block of 8192 elements, relative to the scene), and its present 32-bit words in element order; val_base uint32 [B + 1] the
+ * scenes' prefix into vals [n_vals].  dst f32 [B][n]: the present words unchanged (-0.0, NaN payloads, denormals), +0.0f elsewhere.
+ * Gather indices are clamped to n_vals - 1, so a malformed stream reads nothing outside its buffers.  n a multiple of 32, fewer than
+ * 2^32 elements and values, 4-byte aligned streams, 16-byte aligned dst; STJ_EUNSUPPORTED otherwise, STJ_OK for zero sizes.  No host
+ * synchronisation, no allocation, no atomics: one launch each on `stream`. */
+int stj_unpack_bits(const uint32_t* bits, float* dst, long long n_total, hipStream_t stream);
+int stj_unpack_sparse(const uint32_t* mask, const uint32_t* offs, const uint32_t* val_base, const float* vals, long long n_vals,
+                      float* dst, int B, long long n, hipStream_t stream);
+
 /* trajNet input plumbing (trajNet.py:125-140), one launch: obs [B,n_obs,Tn,8] and occ [B,n_occ,Tn,8] (f32, 16-byte aligned) ->
  * x5 [B*A*Tn,5] node features, v3 [B*A,3] vector features of step 0, vt [B*A,Tn] int32 step-valid (feature 0 != 0), cmi [B*A] int32 /
  * cmf [B*A] (type T) agent-valid (any step valid); A = n_obs + n_occ, obs rows first. */

@@ -33,6 +33,8 @@ SIGNATURES = {
     'stj_time_fold': [vp, vp, cl, vp],
     'stj_fold_parts': [vp, vp, vp, cl, vp],
     'stj_decode_raw': [vp, ci, vp, cl, ci, ci, ci, ci, ci, ci, ci, cf, vp],
+    'stj_unpack_bits': [vp, vp, cl, vp],
+    'stj_unpack_sparse': [vp, vp, vp, vp, cl, vp, ci, cl, vp],
     'stj_metrics': [vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp],
     'stj_rng_advance': [vp, vp],
     'stj_rng_advance_snap': [vp, vp, vp],

@@ -9,6 +9,12 @@ Device side: `decode_batch` uploads the raw feature bytes of a batch and expands
         data = decode_batch(batch, 'cuda')          # dict: ogm [B,512,512,11,2], map_image [B,256,256,3], gt_flow [B,8,256,256,2] ...
 
 A writer (`write_tfrecord`, `serialize_example`) exists for tests and synthetic data; it produces the same bytes TF reads.
+
+Packed records (opt-in): most of those bytes carry no information -- a bool needs one bit, a float plane that is zero almost everywhere
+one bit per cell plus its non-zero words.  `pack_example` rewrites a parsed record into that lossless form once, on the host
+(`pack_bits`, `pack_sparse`; `unpack_reference` states the format and is the only CPU path); `decode_batch_packed` and `PackedFeed` upload
+the packed bytes and expand them on the device (stj_unpack_bits / stj_unpack_sparse) into the same float32 tensors, bit for bit, that
+`decode_batch` and `HostFeed.land()` give for the original record.
 """
 import ctypes
 import struct
@@ -215,7 +221,180 @@ def batches(examples, batch_size):
         yield buf
 
 
+# ---------------------------------------------------------------------------------------------------- packed features (host, NumPy)
+SPARSE_BLOCK = 8192         # elements per block of a sparse plane's `offs` (csrc/unpack.h: UP_BLOCK)
+PACKED_KIND = {'ogm': 'bits', 'gt_obs_ogm': 'bits', 'gt_occ_ogm': 'bits', 'vec_flow': 'sparse', 'gt_flow': 'sparse', 'origin_flow': 'sparse'}
+_RAW_DTYPE = {'bool': np.uint8, 'int8': np.int8, 'float32': '<u4', 'float64': '<f8'}
+
+
+def pack_bits(a):
+    """Any array -> uint32 words: element i (C order) is bit i & 7 of byte i >> 3, LSB first, set iff the element is non-zero; zero
+    bits pad the stream to a whole number of 32-bit words (little-endian words: bit i & 31 of word i >> 5)."""
+    b = np.packbits(np.ascontiguousarray(a).reshape(-1) != 0, bitorder='little')
+    b = np.concatenate([b, np.zeros(-b.size % 4, np.uint8)])
+    return b.view('<u4')
+
+
+def _words(a):
+    a = np.ascontiguousarray(a)
+    if a.dtype.itemsize != 4:
+        raise ValueError(f'pack_sparse: 32-bit elements only, got {a.dtype}')
+    return a.reshape(-1).view(np.uint32)
+
+
+def pack_sparse(a):
+    """float32 (or any 32-bit) array of n elements, n a multiple of 32 -> (mask, offs, vals), all uint32: a word is present iff its
+    32-bit pattern is non-zero (-0.0, NaN payloads and denormals are present and survive unchanged); mask [n / 32] in pack_bits' order;
+    offs [ceil(n / SPARSE_BLOCK) + 1] the exclusive prefix of the present counts per block, offs[-1] the total; vals the present words
+    in element order."""
+    w = _words(a)
+    n = w.size
+    if n % 32:
+        raise ValueError(f'pack_sparse: {n} elements, a multiple of 32 only')
+    present = w != 0
+    nblk = -(-n // SPARSE_BLOCK)
+    counts = np.add.reduceat(present.astype(np.int64), np.arange(0, n, SPARSE_BLOCK)) if n else np.zeros(0, np.int64)
+    offs = np.zeros(nblk + 1, np.uint32)
+    offs[1:] = np.cumsum(counts)
+    return pack_bits(present), offs, w[present].copy()
+
+
+def check_sparse(mask, offs, vals, n, name='sparse'):
+    """ValueError unless (mask, offs, vals) -- arrays or the record's bytes -- are a well-formed sparse plane of n elements: byte
+    lengths, offs starting at 0 and non-decreasing, no block holding more than its element count, offs[-1] values.  -> uint32 arrays."""
+    if n % 32:
+        raise ValueError(f'{name}: {n} elements, a multiple of 32 only')
+    nblk = -(-n // SPARSE_BLOCK)
+    arrs = []
+    for part, x, want in (('mask', mask, n // 8), ('offs', offs, 4 * (nblk + 1)), ('vals', vals, None)):
+        x = np.frombuffer(bytes(x), np.uint8) if not isinstance(x, np.ndarray) else np.ascontiguousarray(x).reshape(-1).view(np.uint8)
+        if x.size % 4 or (want is not None and x.size != want):
+            raise ValueError(f'{name}/{part}: {x.size} bytes' + (f', expected {want}' if want is not None else ', not whole 32-bit words'))
+        arrs.append(x.view('<u4'))
+    mask, offs, vals = arrs
+    d = np.diff(offs.astype(np.int64))
+    if offs[0] != 0 or (d < 0).any():
+        raise ValueError(f'{name}/offs: not a non-decreasing prefix from 0')
+    cap = np.minimum(SPARSE_BLOCK, n - SPARSE_BLOCK * np.arange(nblk))
+    if (d > cap).any():
+        raise ValueError(f'{name}/offs: a block holds more present words than elements')
+    if int(offs[-1]) != vals.size:
+        raise ValueError(f'{name}: offs[-1] = {int(offs[-1])} but vals holds {vals.size} words')
+    return mask, offs, vals
+
+
+def unpack_reference(kind, *args):
+    """The format, stated in code: unpack_reference('bits', bits, n) / unpack_reference('sparse', mask, offs, vals, n) -> float32 [n].
+    bits: 1.0f where bit i & 7 of byte i >> 3 is set, else 0.0f.  sparse: element i is vals[offs[i // SPARSE_BLOCK] + popcount(mask
+    bits of its block below i)] where its mask bit is set, else +0.0f."""
+    if kind == 'bits':
+        bits, n = args
+        by = np.ascontiguousarray(bits).reshape(-1).view(np.uint8)
+        if by.size != 4 * -(-n // 32):
+            raise ValueError(f'bits: {by.size} bytes, expected {4 * -(-n // 32)} for {n} elements')
+        return np.unpackbits(by, bitorder='little')[:n].astype(np.float32)
+    if kind != 'sparse':
+        raise ValueError(f'unpack_reference: kind {kind!r}')
+    mask, offs, vals, n = args
+    mask, offs, vals = check_sparse(mask, offs, vals, n)
+    bit = np.unpackbits(mask.view(np.uint8), bitorder='little')[:n].astype(np.int64)
+    out = np.zeros(n, np.uint32)
+    for blk in range(-(-n // SPARSE_BLOCK)):
+        lo, hi = blk * SPARSE_BLOCK, min(n, (blk + 1) * SPARSE_BLOCK)
+        below = np.cumsum(bit[lo:hi]) - bit[lo:hi]                  # popcount of the block's mask bits below each element
+        idx = int(offs[blk]) + below
+        sel = bit[lo:hi] != 0
+        if sel.any() and int(idx[sel].max()) >= vals.size:
+            raise ValueError('sparse: mask and offs disagree')
+        out[lo:hi][sel] = vals[idx[sel]]
+    return out.view(np.float32)
+
+
+def _decoded(raw, dtype, shape, crop):
+    """The decoded array of a feature: the record's bytes after the reshape and centre crop, before the cast (float32 as uint32 words)."""
+    a = np.frombuffer(bytes(raw), _RAW_DTYPE[dtype])
+    if a.size != int(np.prod(shape)):
+        raise ValueError(f'{a.size * a.itemsize} bytes, expected {int(np.prod(shape)) * ITEMSIZE[dtype]} for {dtype}{list(shape)}')
+    a = a.reshape(shape)
+    if crop is not None:
+        y0, x0, Ho, Wo = crop
+        a = a[:, y0:y0 + Ho, x0:x0 + Wo, :]
+    return a
+
+
+def decoded_shape(shape, crop):
+    return tuple(shape) if crop is None else (shape[0], crop[2], crop[3], shape[3])
+
+
+def pack_example(example, grid=512, out=256, test=False):
+    """A parsed record ({feature: bytes}) -> {feature: bytes} with the bool features as `<name>/bits` and the float32 planes as
+    `<name>/mask`, `<name>/offs`, `<name>/vals` (the ground-truth features already centre-cropped); everything else under its own name.
+    serialize_example / write_tfrecord store the result like any record."""
+    res = {}
+    spec = feature_spec(grid, out, test)
+    for name, raw in example.items():
+        kind = PACKED_KIND.get(name) if name in spec else None
+        if kind is None:
+            res[name] = bytes(raw)
+            continue
+        dtype, shape, crop, _ = spec[name]
+        try:
+            a = _decoded(raw, dtype, shape, crop)
+        except ValueError as e:
+            raise ValueError(f'feature {name}: {e}') from None
+        if a.size % 32:
+            raise ValueError(f'feature {name}: {a.size} elements per scene, a multiple of 32 only')
+        if kind == 'bits':
+            res[name + '/bits'] = pack_bits(a).tobytes()
+        else:
+            mask, offs, vals = pack_sparse(a)
+            res[name + '/mask'], res[name + '/offs'], res[name + '/vals'] = mask.tobytes(), offs.tobytes(), vals.tobytes()
+    return res
+
+
+def unpack_example_reference(packed, grid=512, out=256, test=False):
+    """CPU inverse of pack_example + _parse_image_function, NumPy only: {feature: float32 array}, shaped as decode_batch shapes one
+    scene.  What decode_batch_packed is tested against; not a product path."""
+    res = {}
+    for name, (dtype, shape, crop, scale) in feature_spec(grid, out, test).items():
+        dshape = decoded_shape(shape, crop)
+        n = int(np.prod(dshape))
+        kind = PACKED_KIND.get(name)
+        if kind == 'bits' and name + '/bits' in packed:
+            res[name] = unpack_reference('bits', np.frombuffer(bytes(packed[name + '/bits']), np.uint8), n).reshape(dshape)
+        elif kind == 'sparse' and name + '/mask' in packed:
+            res[name] = unpack_reference('sparse', *(bytes(packed[f'{name}/{p}']) for p in ('mask', 'offs', 'vals')), n).reshape(dshape)
+        else:
+            a = _decoded(packed[name], dtype, shape, crop)
+            a = a.view(np.float32) if dtype == 'float32' else (a != 0) if dtype == 'bool' else a
+            res[name] = a.astype(np.float32) * np.float32(scale)
+    return res
+
+
 # ---------------------------------------------------------------------------------------------------- device decode
+def _decode_raw_feature(examples, name, spec, dev):
+    """One feature of a batch from the record's own bytes: pinned upload + stj_decode_raw (crop, cast, scale)."""
+    dtype, shape, crop, scale = spec
+    B = len(examples)
+    nbytes = int(np.prod(shape)) * ITEMSIZE[dtype]
+    host = torch.empty((B, nbytes), dtype=torch.uint8).pin_memory()
+    for b, ex in enumerate(examples):
+        raw = ex[name]
+        if len(raw) != nbytes:
+            raise ValueError(f'feature {name}: {len(raw)} bytes, expected {nbytes} for {dtype}{list(shape)}')
+        host[b] = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
+    src = host.to(dev, non_blocking=True)
+    if crop is None:
+        n_outer, H, W, C = B, 1, int(np.prod(shape)), 1
+        y0, x0, Ho, Wo = 0, 0, 1, W
+    else:
+        n_outer, H, W, C = B * shape[0], shape[1], shape[2], shape[3]
+        y0, x0, Ho, Wo = crop
+    dst = torch.empty((B,) + decoded_shape(shape, crop), dtype=torch.float32, device=dev)
+    call('stj_decode_raw', _p(src), KIND[dtype], _p(dst), n_outer, H, W, C, y0, x0, Ho, Wo, float(scale), _st())
+    return dst
+
+
 def decode_batch(examples, device='cuda', grid=512, out=256, test=False):
     """examples: list of {feature: bytes} (parse_example output).  Returns float32 tensors on `device`, leading batch axis,
     shaped and cropped as _parse_image_function does (train.py:87-103): ogm [B,g,g,11,2], map_image [B,o,o,3] (/256),
@@ -224,27 +403,83 @@ def decode_batch(examples, device='cuda', grid=512, out=256, test=False):
     dev = torch.device(device)
     if dev.type != 'cuda':
         raise RuntimeError('decode_batch: CUDA (ROCm) device only: the HIP path has no CPU fallback')
+    res = {name: _decode_raw_feature(examples, name, sp, dev) for name, sp in feature_spec(grid, out, test).items()}
+    if test and 'scenario/id' in examples[0]:
+        res['scenario/id'] = [bytes(ex['scenario/id']) for ex in examples]
+    return res
+
+
+def _pinned_words(n):
+    return torch.empty((max(int(n), 1),), dtype=torch.int32).pin_memory()
+
+
+def _put(dst, off, arr):
+    """uint32 array -> words off.. of a (pinned) int32 tensor."""
+    if arr.size:
+        dst.numpy()[off:off + arr.size] = np.ascontiguousarray(arr).view(np.int32)
+
+
+def _batch_sparse(planes, n):
+    """[(mask, offs, vals)] of a batch (checked uint32 arrays) -> pinned int32 tensors mask [B * n/32], offs [B * (nblk + 1)],
+    val_base [B + 1], vals [total] and the total."""
+    B, nw, nb1 = len(planes), n // 32, -(-n // SPARSE_BLOCK) + 1
+    base = np.zeros(B + 1, np.int64)
+    base[1:] = np.cumsum([pl[2].size for pl in planes])
+    mask, offs, vb, vals = _pinned_words(B * nw), _pinned_words(B * nb1), _pinned_words(B + 1), _pinned_words(base[-1])
+    for b, (m, o, v) in enumerate(planes):
+        _put(mask, b * nw, m); _put(offs, b * nb1, o); _put(vals, int(base[b]), v)
+    _put(vb, 0, base.astype(np.uint32))
+    return mask, offs, vb, vals, int(base[-1])
+
+
+def decode_batch_packed(examples, device='cuda', grid=512, out=256, test=False):
+    """decode_batch for records written by pack_example: the same dict, shapes and float32 values, bit for bit.  The packed features
+    cross PCIe as they are stored (a sparse plane: only its used words) and are expanded by stj_unpack_bits / stj_unpack_sparse; the
+    unpacked ones go through stj_decode_raw as in decode_batch.  Every stream is checked on the host before any launch (ValueError)."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError('decode_batch_packed: CUDA (ROCm) device only: the HIP path has no CPU fallback')
     B = len(examples)
-    res = {}
-    for name, (dtype, shape, crop, scale) in feature_spec(grid, out, test).items():
-        nbytes = int(np.prod(shape)) * ITEMSIZE[dtype]
-        host = torch.empty((B, nbytes), dtype=torch.uint8).pin_memory()
-        for b, ex in enumerate(examples):
-            raw = ex[name]
-            if len(raw) != nbytes:
-                raise ValueError(f'feature {name}: {len(raw)} bytes, expected {nbytes} for {dtype}{list(shape)}')
-            host[b] = torch.frombuffer(bytearray(raw), dtype=torch.uint8)
-        src = host.to(dev, non_blocking=True)
-        if crop is None:
-            n_outer, H, W, C = B, 1, int(np.prod(shape)), 1
-            y0, x0, Ho, Wo = 0, 0, 1, W
-            oshape = (B,) + tuple(shape)
+    spec = feature_spec(grid, out, test)
+    todo = []
+    for name, sp in spec.items():                                    # host: check every stream first, NumPy only
+        dtype, shape, crop, scale = sp
+        dshape = decoded_shape(shape, crop)
+        n = int(np.prod(dshape))
+        kind = PACKED_KIND.get(name)
+        if kind == 'bits' and name + '/bits' in examples[0]:
+            if n % 32 or B * n >= 1 << 32:
+                raise ValueError(f'feature {name}: {B} x {n} elements, a multiple of 32 per scene and fewer than 2^32 only')
+            for ex in examples:
+                if len(ex[name + '/bits']) != n // 8:
+                    raise ValueError(f"feature {name}/bits: {len(ex[name + '/bits'])} bytes, expected {n // 8} for {n} elements")
+            todo.append((name, 'bits', dshape, n, None))
+        elif kind == 'sparse' and name + '/mask' in examples[0]:
+            if B * n >= 1 << 32:
+                raise ValueError(f'feature {name}: {B} x {n} elements, fewer than 2^32 only')
+            planes = [check_sparse(*(ex[f'{name}/{p}'] for p in ('mask', 'offs', 'vals')), n, f'feature {name}') for ex in examples]
+            todo.append((name, 'sparse', dshape, n, planes))
         else:
-            n_outer, H, W, C = B * shape[0], shape[1], shape[2], shape[3]
-            y0, x0, Ho, Wo = crop
-            oshape = (B, shape[0], Ho, Wo, C)
-        dst = torch.empty(oshape, dtype=torch.float32, device=dev)
-        call('stj_decode_raw', _p(src), KIND[dtype], _p(dst), n_outer, H, W, C, y0, x0, Ho, Wo, float(scale), _st())
+            for ex in examples:
+                if len(ex[name]) != int(np.prod(shape)) * ITEMSIZE[dtype]:
+                    raise ValueError(f'feature {name}: {len(ex[name])} bytes, expected {int(np.prod(shape)) * ITEMSIZE[dtype]} for {dtype}{list(shape)}')
+            todo.append((name, 'raw', dshape, n, sp))
+    res = {}
+    for name, kind, dshape, n, h in todo:
+        if kind == 'raw':
+            res[name] = _decode_raw_feature(examples, name, h, dev)
+            continue
+        dst = torch.empty((B,) + dshape, dtype=torch.float32, device=dev)
+        if kind == 'bits':
+            host = _pinned_words(B * n // 32)
+            for b, ex in enumerate(examples):
+                _put(host, b * (n // 32), np.frombuffer(bytes(ex[name + '/bits']), '<u4'))
+            src = host.to(dev, non_blocking=True)
+            call('stj_unpack_bits', _p(src), _p(dst), B * n, _st())
+        else:
+            mask, offs, vb, vals, total = _batch_sparse(h, n)
+            d = [t.to(dev, non_blocking=True) for t in (mask, offs, vb, vals)]
+            call('stj_unpack_sparse', _p(d[0]), _p(d[1]), _p(d[2]), _p(d[3]), total, _p(dst), B, n, _st())
         res[name] = dst
     if test and 'scenario/id' in examples[0]:
         res['scenario/id'] = [bytes(ex['scenario/id']) for ex in examples]
@@ -362,3 +597,128 @@ class HostFeed:
         self._stop = True
         self._go.set()
         self._thread.join(timeout=5)
+
+
+class SparseHost:
+    """Pinned host side of one sparse key of a PackedFeed: the packed planes of a batch of B scenes of n elements.  `vals` holds the
+    dense worst case (B n words); `count` is how many of them the current batch uses -- the feed uploads only those.  A loader either
+    calls fill(x) or writes mask / offs / val_base / vals / count itself (between wait_uploaded() and the next land())."""
+
+    def __init__(self, B, n):
+        if n % 32 or B * n >= 1 << 32:
+            raise ValueError(f'SparseHost: {B} x {n} elements, a multiple of 32 per scene and fewer than 2^32 only')
+        self.B, self.n, self.nblk = B, n, -(-n // SPARSE_BLOCK)
+        self.mask, self.offs = _pinned_words(B * n // 32), _pinned_words(B * (self.nblk + 1))
+        self.val_base, self.vals = _pinned_words(B + 1), _pinned_words(B * n)
+        for t in (self.mask, self.offs, self.val_base):
+            t.zero_()
+        self.count = 0
+
+    def fill(self, x):
+        """x: [B, ...] float32 (array or CPU tensor), n elements per scene -> packed in place."""
+        x = x.numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        x = np.ascontiguousarray(x).reshape(self.B, self.n)
+        base = np.zeros(self.B + 1, np.int64)
+        for b in range(self.B):
+            m, o, v = pack_sparse(x[b])
+            _put(self.mask, b * (self.n // 32), m); _put(self.offs, b * (self.nblk + 1), o); _put(self.vals, int(base[b]), v)
+            base[b + 1] = base[b] + v.size
+        _put(self.val_base, 0, base.astype(np.uint32))
+        self.count = int(base[-1])
+        return self
+
+    def parts(self):
+        return {'mask': self.mask, 'offs': self.offs, 'val_base': self.val_base, 'vals': self.vals}
+
+    @property
+    def nbytes(self):
+        """Bytes the feed uploads for the current batch."""
+        return 4 * (self.mask.numel() + self.offs.numel() + self.val_base.numel() + self.count)
+
+
+def bits_host(x):
+    """[B, ...] array / CPU tensor (non-zero = True), a multiple of 32 elements per scene -> pinned int32 words for a 'bits' key."""
+    x = x.numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    if x[0].size % 32:
+        raise ValueError(f'bits_host: {x[0].size} elements per scene, a multiple of 32 only')
+    w = pack_bits(x)
+    h = _pinned_words(w.size)
+    _put(h, 0, w)
+    return h
+
+
+class PackedFeed(HostFeed):
+    """HostFeed whose host side may be packed: same protocol (start / land / wait_uploaded / close), same worker thread, copy stream
+    and 1.5 MB pieces; works on GraphedTrainStep.static and GraphedForward.static alike.
+
+        feed = PackedFeed(step.static, host, packed={'ogm': 'bits', 'flow': 'sparse'}, raw={'map_img': 'int8'})
+
+    host[k] for a 'bits' key: pinned int32 words (bits_host; pack_bits of the batch, static[k].numel() / 32 of them); for a 'sparse' key:
+    a SparseHost -- its mask, offs and val_base are uploaded whole and of `vals` only the first `count` words, read when the upload
+    starts.  land() expands both into static[k] (stj_unpack_bits / stj_unpack_sparse); the other keys behave as in HostFeed."""
+
+    def __init__(self, static, host, packed=None, raw=None, chunk_bytes=3 << 19):
+        self.packed = {k: v for k, v in (packed or {}).items() if k in static and k in host}
+        for k, kind in self.packed.items():
+            B, numel = static[k].shape[0], static[k].numel()
+            if kind == 'bits':
+                if (numel // B) % 32 or host[k].numel() * host[k].element_size() * 8 != numel:
+                    raise ValueError(f'PackedFeed: host[{k!r}] must hold {numel} bits, a multiple of 32 per scene')
+            elif kind == 'sparse':
+                if not isinstance(host[k], SparseHost) or (host[k].B, host[k].n) != (B, numel // B):
+                    raise ValueError(f'PackedFeed: host[{k!r}] must be a SparseHost({B}, {numel // B})')
+            else:
+                raise ValueError(f'PackedFeed: packed kind {kind!r}')
+        self.sparse = {k: host[k] for k, kind in self.packed.items() if kind == 'sparse'}
+        self._n_vals = {k: 0 for k in self.sparse}
+        super().__init__(static, {k: h for k, h in host.items() if k not in self.sparse}, raw, chunk_bytes)
+        for k, sh in self.sparse.items():
+            for part, h in sh.parts().items():
+                if not h.is_pinned():
+                    raise ValueError(f'PackedFeed: host[{k!r}].{part} must be pinned memory')
+        self.sparse_stage = {k: {part: torch.empty(h.shape, dtype=h.dtype, device=self.dev) for part, h in sh.parts().items()}
+                             for k, sh in self.sparse.items()}
+
+    def _pieces(self, hs, ss, n):
+        step = max(1, self.chunk // hs.element_size())
+        for i in range(0, n, step):
+            j = min(n, i + step)
+            ss[i:j].copy_(hs[i:j], non_blocking=True)
+
+    def _upload(self):
+        with torch.cuda.stream(self.copy):
+            self.copy.wait_event(self.landed)
+            for k, h in self.host.items():
+                self._pieces(h.view(-1), self.stage[k].view(-1), h.numel())
+            for k, sh in self.sparse.items():
+                count = min(int(sh.count), sh.vals.numel())
+                self._n_vals[k] = count                                    # read by the land() of THIS batch, before the next upload starts
+                for part, h in sh.parts().items():
+                    self._pieces(h, self.sparse_stage[k][part], count if part == 'vals' else h.numel())
+            self.up.record(self.copy)
+
+    def land(self):
+        self._enqueued.wait(); self._enqueued.clear()
+        self._check()
+        main = torch.cuda.current_stream(self.dev)
+        main.wait_event(self.up)
+        kind = {'bool': 0, 'int8': 1}
+        for k, st in self.stage.items():
+            dst = self.static[k]
+            n = dst.numel()
+            if self.packed.get(k) == 'bits':
+                call('stj_unpack_bits', _p(st), _p(dst), n, _st())
+            elif k in self.raw:
+                call('stj_decode_raw', _p(st), kind[self.raw[k]], _p(dst), 1, 1, n, 1, 0, 0, 1, n, (1.0 / 256.0) if self.raw[k] == 'int8' else 1.0, _st())
+            else:
+                dst.copy_(st, non_blocking=True)
+        for k, st in self.sparse_stage.items():
+            dst = self.static[k]
+            B = dst.shape[0]
+            call('stj_unpack_sparse', _p(st['mask']), _p(st['offs']), _p(st['val_base']), _p(st['vals']), self._n_vals[k], _p(dst), B, dst.numel() // B, _st())
+        self.landed.record(main)
+        self._go.set()
+
+    def upload_bytes(self):
+        """Bytes the next upload moves, as the host buffers stand."""
+        return sum(h.numel() * h.element_size() for h in self.host.values()) + sum(sh.nbytes for sh in self.sparse.values())
