@@ -1163,8 +1163,6 @@ template <typename T> static size_t int_attn_bwd_lds() {
 }  // namespace agf
 
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
-#include "agent_fused_abi.h"
-
 extern "C" long long stj_agent_pack_workspace_bytes(int dtype) { return agf::P_TOTAL * (dtype == STJ_F32 ? 4 : 2); }
 
 extern "C" int stj_agent_pack(const stj_agent_weights* w, void* out, int dtype, hipStream_t stream) {

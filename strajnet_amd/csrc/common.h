@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/strajnet_hip.h"      // the C ABI: every extern "C" definition is compiled against its prototype
 
 #define STJ_WAVE 64
 
@@ -108,7 +109,7 @@ __device__ __forceinline__ void ld4(const f16* p, float* v) {
 __device__ __forceinline__ void ld4(const float* p, float* v) { const float4 u = *reinterpret_cast<const float4*>(p); v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w; }
 
 // ---- activations -----------------------------------------------------------------------
-enum { ACT_NONE = 0, ACT_GELU = 1, ACT_ELU = 2 };
+enum { ACT_NONE = STJ_ACT_NONE, ACT_GELU = STJ_ACT_GELU, ACT_ELU = STJ_ACT_ELU };
 
 __device__ __forceinline__ float gelu_f(float x) {   // tanh form (reference modules.py:18-29)
   const float k = 0.7978845608028654f;
@@ -145,7 +146,7 @@ __device__ __forceinline__ float apply_act(float x, int act) {
 }
 
 // ---- unary activations of stj_unary_fwd / _bwd (csrc/util.hip) and of the kernels that fuse them ----
-enum { U_GELU = 1, U_ELU = 2, U_TANHS = 3 };
+enum { U_GELU = STJ_U_GELU, U_ELU = STJ_U_ELU, U_TANHS = STJ_U_TANH_SCALE };
 // The op is a template parameter (no per-element selection) and the bf16 kernels use a v_exp_f32 based tanh (abs error ~2e-7,
 // two decades below bf16 resolution); the f32 parity mode keeps libm tanhf / expm1f.
 template <bool FAST> __device__ __forceinline__ float tanh_sel(float u) {
@@ -312,8 +313,6 @@ __device__ __forceinline__ float pad_at(const float* img, int H, int W, int es, 
 
 
 // ---- host-side error plumbing -------------------------------------------------------------
-enum { STJ_OK = 0, STJ_EINVAL = -1, STJ_ELAUNCH = -2, STJ_EUNSUPPORTED = -3 };
-enum { STJ_F32 = 0, STJ_BF16 = 1, STJ_F16 = 2 };
 static inline bool stj_is16(int dtype) { return dtype == STJ_BF16 || dtype == STJ_F16; }
 static inline bool stj_dtype_ok(int dtype) { return dtype == STJ_F32 || dtype == STJ_BF16 || dtype == STJ_F16; }
 void stj_set_error(const char* fmt, ...);

@@ -18,7 +18,6 @@
 // launch): in training the forward writes the im2col matrix from its halo tile, and the backward writes dc.
 // Roundings follow the layer-by-layer chain (each layer's output in the storage dtype), so both paths agree to the summation order.
 #include "common.h"
-#include "fgoff_fused_abi.h"
 
 namespace fgo {
 constexpr int G = 8, GC = 48, C = G * GC, KK = 9 * GC;      // groups, channels per group, 384, 432 = contraction length per group

@@ -313,13 +313,6 @@ __global__ __launch_bounds__(64 * Geo<TN>::NWV, TN == 96 ? 2 : 1) void wgrad_sk_
 }  // namespace wsk
 
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------
-struct stj_wgrad_job {
-  const void* x; const void* dy; float* dw; float* db;
-  int rows, cin, cout, nb1, nb2;
-  long long ldx, lddy, lddw;
-  long long sx1, sx2, sdy1, sdy2, sdw1, sdw2, sdb1, sdb2;
-};
-
 static bool wsk_supported(const stj_wgrad_job& j, int dtype) {
   if (!stj_is16(dtype)) return false;
   if (j.rows <= 0 || j.rows % wsk::KU || j.cin <= 0 || j.cout <= 0 || j.cin % 8 || j.cout % 8 || j.nb1 <= 0 || j.nb2 <= 0) return false;

@@ -14,7 +14,7 @@ import threading
 import torch
 
 from . import prof
-from ._lib import call as _raw_call
+from ._lib import call as _raw_call, ENUMS as _ENUMS
 
 
 def call(name, *args):
@@ -84,12 +84,11 @@ class gemm_group:
         return False
 
 
-ACT_NONE, ACT_GELU, ACT_ELU = 0, 1, 2
-U_GELU, U_ELU, U_TANHS = 1, 2, 3
+# the header's enums (include/strajnet_hip.h, read by _lib)
+ACT_NONE, ACT_GELU, ACT_ELU = (_ENUMS['stj_act'][k] for k in ('STJ_ACT_NONE', 'STJ_ACT_GELU', 'STJ_ACT_ELU'))
+U_GELU, U_ELU, U_TANHS = (_ENUMS['stj_unary'][k] for k in ('STJ_U_GELU', 'STJ_U_ELU', 'STJ_U_TANH_SCALE'))
+DTYPE_CODE = {t: _ENUMS['stj_dtype'][k] for t, k in ((torch.float32, 'STJ_F32'), (torch.bfloat16, 'STJ_BF16'), (torch.float16, 'STJ_F16'))}
 vp = ctypes.c_void_p
-
-
-DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}      # STJ_F32 / STJ_BF16 / STJ_F16 (strajnet_hip.h)
 
 
 def _dt(t):

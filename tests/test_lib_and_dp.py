@@ -28,16 +28,84 @@ def test_library_exports_every_header_symbol(lib_built):
     assert _lib.lib().stj_abi_version() == 1
 
 
-def test_header_argument_counts_match_binding():
-    """Every prototype in the header has as many parameters as the ctypes signature table."""
+_TOY_HEADER = """
+/* a block comment (with parentheses); a semicolon; and a prototype: int stj_in_block(int x); */
+// a line comment (too); int stj_in_line(void);
+enum stj_kind { STJ_KA = 0, STJ_KB = -3 };
+const char* stj_last_error(void);
+int stj_none(void);
+long long stj_bytes(long long M, int C);      /* trailing (comment); */
+int stj_multi(const void* a, const long long* rng,      // split (over
+              float p, int* out,                        //  several); lines
+              hipStream_t stream);
+typedef struct stj_blk {
+  int a, b, c;                      /* three (ints); */
+  const float* x; void* y; long long n; float p, q;      // several members; one line
+} stj_blk;
+int stj_takes(const stj_blk* blk, hipStream_t stream);
+"""
+
+
+def test_header_reader_pinned():
+    """read_header on a header written for the purpose: the exact ctypes of every prototype, struct field and enumerator, and a refusal of
+    any type outside its table."""
+    from ctypes import c_float as cf, c_int as ci, c_longlong as cl, c_void_p as vp
+    from strajnet_amd._lib import StjError, read_header
+    sigs, rets, structs, enums = read_header(_TOY_HEADER)
+    assert sigs == {'stj_none': [], 'stj_bytes': [cl, ci], 'stj_multi': [vp, vp, cf, vp, vp], 'stj_takes': [vp, vp]}
+    assert rets == {'stj_none': ci, 'stj_bytes': cl, 'stj_multi': ci, 'stj_takes': ci}
+    assert structs == {'stj_blk': [('a', ci), ('b', ci), ('c', ci), ('x', vp), ('y', vp), ('n', cl), ('p', cf), ('q', cf)]}
+    assert enums == {'stj_kind': {'STJ_KA': 0, 'STJ_KB': -3}}
+    for bad, where in (('int stj_bad(const void* a, unsigned n);', 'stj_bad'), ('int stj_bad(int);', 'stj_bad'),
+                       ('typedef struct stj_s { int a; unsigned n; } stj_s;', 'stj_s'), ('typedef struct stj_s { int a[4]; } stj_s;', 'stj_s'),
+                       ('typedef struct stj_s { float *a, *b; } stj_s;', 'stj_s')):
+        with pytest.raises(StjError, match=where):
+            read_header(_TOY_HEADER + bad)
+
+
+_BLOCKS = {'stj_wgrad_job': 'WgradJob', 'stj_agent_weights': 'AgentWeights', 'stj_agent_enc_args': 'AgentEncArgs',
+           'stj_agent_int_args': 'AgentIntArgs', 'stj_fgoff_args': 'FgOffArgs'}
+
+
+def test_struct_layout_matches_the_compiler(tmp_path):
+    """sizeof and every offsetof of the five argument blocks, printed by a host program the library's compiler builds from the header,
+    equal what ctypes lays out from the parsed field lists."""
+    import ctypes
+    from strajnet_amd import _lib, build
+    assert set(_lib.STRUCTS) == set(_BLOCKS) and sum(len(f) for f in _lib.STRUCTS.values()) == 152
+    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{_lib.HEADER_PATH}"', 'int main() {']
+    want = []
+    for sname, cname in _BLOCKS.items():
+        cls = getattr(_lib, cname)
+        assert cls._fields_ == _lib.STRUCTS[sname]
+        lines.append(f'  printf("{sname} %zu\\n", sizeof({sname}));')
+        want.append(f'{sname} {ctypes.sizeof(cls)}')
+        for f, _ in cls._fields_:
+            lines.append(f'  printf("{sname}.{f} %zu\\n", offsetof({sname}, {f}));')
+            want.append(f'{sname}.{f} {getattr(cls, f).offset}')
+    src = tmp_path / 'layout.cpp'
+    src.write_text('\n'.join(lines + ['  return 0;', '}', '']))
+    exe = tmp_path / 'layout'
+    r = subprocess.run([build._hipcc(), '-std=c++17', str(src), '-o', str(exe)], capture_output=True, text=True)        # .cpp: host only
+    assert r.returncode == 0, r.stderr[-3000:]
+    got = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split('\n')[:-1]
+    assert len(got) == 152 + 5 and got == want
+
+
+def test_struct_pointer_parameters_are_pointers():
+    """A prototype that takes one of the five argument blocks takes it by pointer, and the binding passes a pointer there."""
+    import ctypes
     from strajnet_amd import _lib
-    hdr = open(os.path.join(ROOT, 'include', 'strajnet_hip.h')).read()
-    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
-    for name, args in _lib.SIGNATURES.items():
-        m = re.search(r'\b(?:int|long long)\s+' + name + r'\s*\((.*?)\)\s*;', hdr, flags=re.S)
-        assert m, name
-        params = [p for p in m.group(1).split(',') if p.strip() and p.strip() != 'void']
-        assert len(params) == len(args), (name, len(params), len(args))
+    hdr = re.sub(r'/\*.*?\*/', '', open(_lib.HEADER_PATH).read(), flags=re.S)
+    seen = set()
+    for name, params in re.findall(r'\b(stj_\w+)\s*\(([^()]*)\)\s*;', hdr):
+        for i, p in enumerate(params.split(',')):
+            for sname in _BLOCKS:
+                if re.search(r'\b' + sname + r'\b', p):
+                    assert re.fullmatch(r'\s*const\s+' + sname + r'\s*\*\s*\w+\s*', p), (name, p)
+                    assert _lib.SIGNATURES[name][i] is ctypes.c_void_p, (name, i)
+                    seen.add(sname)
+    assert seen == set(_BLOCKS)
 
 
 def test_product_has_no_cpu_fallback():
