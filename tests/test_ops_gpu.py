@@ -150,7 +150,8 @@ def test_layernorm(dt, rows, C, eps):
 @pytest.mark.parametrize('dt', DTYPES)
 @pytest.mark.parametrize('rows,C', [(300, 96), (257, 384), (64, 100)])
 def test_layernorm_res(dt, rows, C):
-    """LayerNorm(x) + res from one pass (v2 vector path and, for C = 100, the v1 path); d res = dy."""
+    """LayerNorm(x) + res from one pass (v2 vector path; C = 100 is the scalar v1 path in the 16-bit types only -- in f32 100 is a whole
+    number of 4-element vectors and takes v2 too; test_layernorm_gpu.py reaches v1 in every type); d res = dy."""
     from strajnet_amd import ops
     pg, pb = mk_param((C,), dt, 0.3, 1), mk_param((C,), dt, 0.3, 2)
     x = rnd((rows, C), dt, 3, 2.0).requires_grad_(True)
