@@ -190,7 +190,8 @@ int stj_swin_attn_bwd(const void* x, const void* dy, const void* qkv, const floa
  *     k, v [Z,B,64,126] = key Wk[z], key Wv[z] (stj_gemm); kvalid int32 [B,64] or NULL; bo/g1/be1 [128], b1 [512], b2/g2/be2 [384]
  *     f32 vectors of set 0.  rng_state != NULL: training, the three dropout sites draw with the layouts [Z,B,3,HW,64],
  *     [Z,B*HW,512], [Z,B*HW,384] (as stj_dropout would).  sq, so [Z,B,HW,144], sv1 [.,128], su2 [.,384]: saves for backward
- *     (all or none; NULL for inference).  HW % 64 == 0.
+ *     (all or none; NULL for inference).  HW % 64 == 0.  The f32 vectors bo, g1, be1, b1, b2, g2, be2 must be 16-byte aligned (here and in
+ *     stj_xattn_bwd) and zstride % 4 == 0: the kernels read them as float4.
  *   stj_xattn_bwd: reads dy, query, k, v, sq, sv1, su2 and the pack; writes dquery, dk, dv (via the f32 per-tile partials dkp / dvp,
  *     stj_xattn_bwd_workspace_bytes(Z,B,HW) bytes each, reduced by a second launch) and the operands of the weight-gradient
  *     stj_gemm launches the caller makes: hd, dpre [Z,B,HW,512], du2 [.,384], n1, dv1 [.,128], dq [.,144]
