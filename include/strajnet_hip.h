@@ -145,8 +145,13 @@ int stj_win_attn_bwd(const void* qkv, const float* table, const void* dout, void
  *       slab (write-through stores) and draws a ticket from the unit's arrival counter; the workgroup that draws the last one adds the
  *       other slab and runs the epilogue.  The counters live behind the partial-sum region and re-arm themselves (hence "zeroed once").
  *   REQUIRED at C = 384 (STJ_EINVAL without it); at C = 192 NULL selects one workgroup per unit.  The four stj_swin_* entry points share
- *   the workspace layout (launches that share a workspace must be ordered on one stream); stj_swin_attn_* at C = 384 also need a 16-bit
- *   dtype: (window, 2 of the 12 heads) workgroups. */
+ *   the workspace layout (launches that share a workspace must be ordered on one stream); stj_swin_attn_* at C = 384 run (window, 2 of the
+ *   12 heads) workgroups + a finishing launch (every dtype; in f32 the Wqkv slice of a head is staged in two halves), or two slices of six
+ *   heads that meet inside the launch (16-bit, more than 48 windows).  The arrival counters are the last 16384 bytes of the workspace: 4096
+ *   units per launch (stj_swin_attn_bwd at C = 384, 16-bit, with more windows: STJ_EUNSUPPORTED) and all zero again behind every call.
+ * Preconditions the kernels rely on and the host does not check: every activation, weight and output pointer, gamma, b2, bproj and ws
+ *   16-byte aligned (rows and vectors are read as 16-byte pieces); rows_per_sample a positive multiple of 16 (checked: STJ_EINVAL);
+ *   part_stride >= C. */
 long long stj_swin_split_workspace_bytes(long long M, int C);
 int stj_swin_mlp_fwd(const void* x, const float* gamma, const float* beta, const void* w1, const float* b1, const void* w2,
                      const float* b2, void* y, long long M, int C, float eps, const long long* rng_state, int site,

@@ -955,7 +955,8 @@ def test_swin_mlp_fused(dt, B, N, C, p_drop):
     """csrc/swin_fused.hip: x + DropPath(fc2(gelu(fc1(LN(x))))) in one kernel, and its backward (dx, LN gamma/beta, both weight
     and bias gradients) vs float64 autograd on the same statement (modules.py:260, :40-46, :18-29, :137-151).  Row counts that
     are not a multiple of the block's rows exercise the tail guards.  C = 384 runs the split form: (row block, hidden slice)
-    workgroups + the finishing launch; C = 192 below 32768 rows the form whose two hidden slices meet inside the launch."""
+    workgroups + the finishing launch; C = 192 below 32768 rows the form whose two hidden slices meet inside the launch.
+    (Per dispatch path, through the raw C ABI and judged per row against float64: tests/test_swin_abi_gpu.py with _swin_cases.py.)"""
     from strajnet_amd import ops
     pg, pb = mk_param((C,), dt, 0.3, 1), mk_param((C,), dt, 0.3, 2)
     with torch.no_grad():
@@ -990,7 +991,8 @@ def test_swin_mlp_fused(dt, B, N, C, p_drop):
 @pytest.mark.parametrize('B,N', [(8, 4096), (32, 4096)])
 def test_swin_mlp_fused_c96_wide_row_counts(B, N):
     """The eight-wave 128-row form of the C = 96 MLP kernels, which the op-level test above never reaches: 32768 rows (the bench's stage 0:
-    192-column weight chunks since round 6) and 131072 rows (B = 32 inference / cfg-512: 96-column chunks), bf16 against float64."""
+    192-column weight chunks since round 6) and 131072 rows (B = 32 inference / cfg-512: 96-column chunks), bf16 against float64.
+    (Per dispatch path, through the raw C ABI and judged per row against float64: tests/test_swin_abi_gpu.py with _swin_cases.py.)"""
     test_swin_mlp_fused(torch.bfloat16, B, N, 96, 0.3)
 
 
@@ -999,7 +1001,8 @@ def test_swin_mlp_fused_c96_wide_row_counts(B, N):
                                                   (3, 16, 384, 4, 0.3), (1, 16, 384, 0, 0.0), (2, 8, 384, 0, 0.3), (1, 64, 384, 4, 0.3), (8, 32, 192, 4, 0.3)])
 def test_swin_attn_half_fused(dt, B, res, C, shift, p_drop):
     """csrc/swin_fused.hip: x + DropPath(proj(window_attention(LN(x) Wqkv + b))) in one kernel (modules.py:225-258,103-134,189-216)
-    and its backward (GEMMs + window-attention backward on the saved operands) vs float64 autograd on the index formulation."""
+    and its backward (GEMMs + window-attention backward on the saved operands) vs float64 autograd on the index formulation.
+    (Per dispatch path, through the raw C ABI and judged per row against float64: tests/test_swin_abi_gpu.py with _swin_cases.py.)"""
     from strajnet_amd import ops
     heads = C // 32
     N = res * res
@@ -1047,7 +1050,8 @@ def test_swin_attn_half_fused(dt, B, res, C, shift, p_drop):
 def test_swin384_block_split_vs_layerwise_vs_f64(dt, B, res, shift):
     """One whole C = 384 Swin block (the 16 x 16 stage of cfg-256, the 32 x 32 stage of cfg-512): the split fused kernels
     ((window, head slice) / (row block, hidden slice) workgroups + finishing launches) against float64, and never noticeably
-    further from it than the layer-by-layer HIP path on the same operands -- output, dx and all 13 parameter gradients."""
+    further from it than the layer-by-layer HIP path on the same operands -- output, dx and all 13 parameter gradients.
+    (Per dispatch path, through the raw C ABI and judged per row against float64: tests/test_swin_abi_gpu.py with _swin_cases.py.)"""
     from strajnet_amd import ops
     C, heads, N = 384, 12, res * res
     names = ['g1', 'b1n', 'wq', 'bq', 'tab', 'wp', 'bp', 'g2', 'b2n', 'w1', 'bb1', 'w2', 'bb2']
