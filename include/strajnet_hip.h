@@ -241,7 +241,10 @@ int stj_small_attn_bwd(const void* q, const void* k, const void* v, const int* q
  * + ELU, the 4-head tfa self-attention over the 11 steps with the (x != 0) mask and dropout on the coefficients, GlobalMaxPooling1D,
  * Dense(3 -> 64) on the step-0 type one-hot, concat, Dense(384 -> 384) + ELU.  Forward writes enc and the agent mask cmi, and, when the
  * five s_* pointers are given, what backward reads.  Backward writes the three dY tensors whose weight gradients are the CALLER's
- * (dW += X^T dY through stj_wgrad_group / stj_gemm with X = s_cat / s_att / s_nodes) and accumulates the 5 x 64, 64 and 3 x 64 ones itself. */
+ * (dW += X^T dY through stj_wgrad_group / stj_gemm with X = s_cat / s_att / s_nodes) and accumulates the 5 x 64, 64 and 3 x 64 ones itself.
+ * A step is valid where its RAW float32 x differs from 0 (tf.not_equal(x, 0): -0.0 is invalid, a value that rounds to 0 in the activation
+ * dtype is valid).  bo and bs are read as float4: 16-byte aligned; so are the d_enc_f32 slabs (each slab, i.e. B (n_obs + n_occ) 384 floats
+ * from a 16-byte aligned base).  The pack, the natural-layout 16-bit kernels and every activation tensor are read or written 16 bytes at a time. */
 typedef struct stj_agent_weights {          /* f32 masters (views of the flat parameter buffer), Keras / tfa layouts */
   const float* e_wq; const float* e_wk; const float* e_wv;     /* traj_encoder/node_attention query | key | value kernels [4][64][64] */
   const float* e_wo;                                            /* .../projection_kernel [4][64][320] */
@@ -299,7 +302,10 @@ int stj_agent_enc_bwd(const stj_agent_enc_args* a, hipStream_t stream);
  * in a fixed order (no atomics on activations: bitwise reproducible) -- and a row-wise tail.  stj_agent_enc_bwd takes d_enc with d_enc_f32 = 7.
  * 16-bit dtypes, 64 agents per scene (stj_agent_int_supported); the f32 parity mode keeps the layer-by-layer chain.  Forward writes key
  * [B 64][384] and, when the eleven s_* pointers are given, what backward reads.  Backward writes d_enc and the six dY tensors whose weight
- * gradients are the caller's (X = s_qin / s_concat / s_concat / s_att / s_n1 / s_h), and accumulates seg_embed and the LayerNorm parameters. */
+ * gradients are the caller's (X = s_qin / s_concat / s_concat / s_att / s_n1 / s_h), and accumulates seg_embed and the LayerNorm parameters.
+ * The slabs ws_v1, ws_u2, ws_dn1 and d_enc need no zeroing: every element is written (plain stores) before the next launch reads it.
+ * Alignment: b1 is read as float4 and the four slab workspaces as float4 / float2: 16-byte aligned; bo, g1, be1, b2, g2, be2 and the
+ * obs_norm | occ_norm vectors are read one float at a time (4-byte aligned). */
 int stj_agent_int_supported(int n_obs, int n_occ, int dtype);
 int stj_agent_int_fwd(const stj_agent_int_args* a, hipStream_t stream);
 int stj_agent_int_bwd(const stj_agent_int_args* a, hipStream_t stream);

@@ -265,12 +265,13 @@ __global__ __launch_bounds__(256) void agent_enc_fwd_kernel(EncArgs p) {
 
   for (int i = tid; i < R * 8; i += 256) {               // (values as the storage type holds them: the layer-by-layer path's stj_agent_prep casts the tracks)
     const int row = i >> 3, ag = row / TP, t = row % TP;
-    x8[i] = t < TN ? rnd<T>(track(p, a0 + ag)[t * 8 + (i & 7)]) : 0.f;
+    const float raw = t < TN ? track(p, a0 + ag)[t * 8 + (i & 7)] : 0.f;
+    x8[i] = rnd<T>(raw);
+    if ((i & 7) == 0) vt[row] = raw != 0.f;              // step valid: the RAW float32 x (tf.not_equal(x, 0); stj_agent_prep), not the rounded one
   }
   for (int i = tid; i < 16 * E::LDQ; i += 256) stf(QKV + R * E::LDQ + i, 0.f);
   for (int i = tid; i < 16 * E::LDC; i += 256) stf(CAT + i, 0.f);
   __syncthreads();
-  if (tid < R) vt[tid] = (tid % TP) < TN && x8[tid * 8] != 0.f;
   // nodes = ELU(x[:, :5] Wn + bn)   (Conv1D kernel size 1)
   for (int i = tid; i < R * NF; i += 256) {
     const int row = i / NF, c = i % NF;
@@ -398,13 +399,14 @@ __global__ __launch_bounds__(256) void agent_enc_bwd_kernel(EncArgs p) {
 
   for (int i = tid; i < R * 8; i += 256) {
     const int row = i >> 3, ag = row / TP, t = row % TP;
-    x8[i] = t < TN ? rnd<T>(track(p, a0 + ag)[t * 8 + (i & 7)]) : 0.f;
+    const float raw = t < TN ? track(p, a0 + ag)[t * 8 + (i & 7)] : 0.f;
+    x8[i] = rnd<T>(raw);
+    if ((i & 7) == 0) vt[row] = raw != 0.f;              // as the forward: the raw float32 x
   }
   for (int i = tid; i < (R + 16) * E::LDA; i += 256) stf(DATT + i, 0.f);
   for (int i = tid; i < R * E::LDN; i += 256) stf(Xn + i, 0.f);
   for (int i = tid; i < 16 * E::LDC; i += 256) stf(DS + i, 0.f);
   __syncthreads();
-  if (tid < R) vt[tid] = (tid % TP) < TN && x8[tid * 8] != 0.f;
   for (int i = tid; i < AG * TN * (NF / V); i += 256) {
     const int r = i / (NF / V), c = (i % (NF / V)) * V, ag = r / TN, t = r % TN;
     *reinterpret_cast<uint4*>(Xn + (ag * TP + t) * E::LDN + c) =

@@ -87,7 +87,7 @@ def _rel(a, b):
     return float((a - b).abs().max() / (b.abs().max() + 1e-30))
 
 
-@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize('training', [False, True])
 def test_agent_branch_fused_vs_f64_and_layerwise(dtype, training):
     B = 3
