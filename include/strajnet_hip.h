@@ -11,7 +11,8 @@
  *   - dtype: STJ_F32 = 0 (exact-f32 MFMA, parity mode), STJ_BF16 = 1 (bf16 storage, f32 accumulate: the training throughput
  *     mode) or STJ_F16 = 2 (fp16 storage, f32 accumulate: the inference mode of BASELINE config 4; every entry point accepts it,
  *     the backward ones without any loss scaling and through the generic conv kernels) selects the activation type `T`; parameters, biases, LN gamma/beta, tables and all gradients of parameters are f32.
- *   - return 0 on success, negative stj_status otherwise; message via stj_last_error() (thread local).
+ *   - return 0 on success, negative stj_status otherwise; message via stj_last_error() (thread local).  A `dtype` outside
+ *     enum stj_dtype is STJ_EINVAL (nothing is launched) unless an entry documents STJ_EUNSUPPORTED for it.
  *   - tensors are NHWC / row-major exactly as in the reference.
  *   - "+=" outputs are ACCUMULATED with f32 atomics (they point into the flat gradient buffer).
  */

@@ -1165,7 +1165,7 @@ template <typename T> static size_t int_attn_bwd_lds() {
 }  // namespace agf
 
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
-extern "C" long long stj_agent_pack_workspace_bytes(int dtype) { return agf::P_TOTAL * (dtype == STJ_F32 ? 4 : 2); }
+extern "C" long long stj_agent_pack_workspace_bytes(int dtype) { return agf::P_TOTAL * stj_elem_bytes(dtype); }
 
 extern "C" int stj_agent_pack(const stj_agent_weights* w, void* out, int dtype, hipStream_t stream) {
   if (!w || !out) { stj_set_error("stj_agent_pack: null pointer"); return STJ_EINVAL; }
@@ -1186,10 +1186,9 @@ extern "C" int stj_agent_pack(const stj_agent_weights* w, void* out, int dtype, 
     if (!a.j[i].src) { stj_set_error("stj_agent_pack: weight %d is NULL", i); return STJ_EINVAL; }
   a.out = out;
   const dim3 grid(64, NPACK);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(agent_pack_kernel<bf16>, grid, dim3(256), 0, stream, a);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(agent_pack_kernel<f16>, grid, dim3(256), 0, stream, a);
-  else if (dtype == STJ_F32) hipLaunchKernelGGL(agent_pack_kernel<float>, grid, dim3(256), 0, stream, a);
-  else { stj_set_error("stj_agent_pack: bad dtype %d", dtype); return STJ_EINVAL; }
+  if (!stj_with_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(agent_pack_kernel<typename decltype(t)::type>, grid, dim3(256), 0, stream, a); })) {
+    stj_set_error("stj_agent_pack: bad dtype %d", dtype); return STJ_EINVAL;
+  }
   return stj_check_launch("stj_agent_pack");
 }
 
@@ -1245,17 +1244,17 @@ extern "C" int stj_agent_enc_fwd(const stj_agent_enc_args* s, hipStream_t stream
   agf::EncArgs a;
   const int rc = enc_args(s, a, false);
   if (rc) return rc > 0 ? STJ_OK : rc;
-  if (s->dtype == STJ_BF16) return enc_launch<bf16, false>(a, stream);
-  if (s->dtype == STJ_F16) return enc_launch<f16, false>(a, stream);
-  return enc_launch<float, false>(a, stream);
+  int r = STJ_EUNSUPPORTED;      // (enc_args: a known dtype)
+  stj_with_dtype(s->dtype, [&](auto t) { r = enc_launch<typename decltype(t)::type, false>(a, stream); });
+  return r;
 }
 extern "C" int stj_agent_enc_bwd(const stj_agent_enc_args* s, hipStream_t stream) {
   agf::EncArgs a;
   const int rc = enc_args(s, a, true);
   if (rc) return rc > 0 ? STJ_OK : rc;
-  if (s->dtype == STJ_BF16) return enc_launch<bf16, true>(a, stream);
-  if (s->dtype == STJ_F16) return enc_launch<f16, true>(a, stream);
-  return enc_launch<float, true>(a, stream);
+  int r = STJ_EUNSUPPORTED;      // (enc_args: a known dtype)
+  stj_with_dtype(s->dtype, [&](auto t) { r = enc_launch<typename decltype(t)::type, true>(a, stream); });
+  return r;
 }
 
 extern "C" int stj_agent_int_supported(int n_obs, int n_occ, int dtype) { return n_obs >= 0 && n_occ >= 0 && n_obs + n_occ == agf::NA && stj_is16(dtype); }
@@ -1322,11 +1321,15 @@ extern "C" int stj_agent_int_fwd(const stj_agent_int_args* s, hipStream_t stream
   agf::IntArgs a;
   const int rc = int_args(s, a, false);
   if (rc) return rc > 0 ? STJ_OK : rc;
-  return s->dtype == STJ_BF16 ? int_launch<bf16, false>(a, stream) : int_launch<f16, false>(a, stream);
+  int r = STJ_EUNSUPPORTED;      // (int_args: a 16-bit dtype)
+  stj_with_dtype16(s->dtype, [&](auto t) { r = int_launch<typename decltype(t)::type, false>(a, stream); });
+  return r;
 }
 extern "C" int stj_agent_int_bwd(const stj_agent_int_args* s, hipStream_t stream) {
   agf::IntArgs a;
   const int rc = int_args(s, a, true);
   if (rc) return rc > 0 ? STJ_OK : rc;
-  return s->dtype == STJ_BF16 ? int_launch<bf16, true>(a, stream) : int_launch<f16, true>(a, stream);
+  int r = STJ_EUNSUPPORTED;      // (int_args: a 16-bit dtype)
+  stj_with_dtype16(s->dtype, [&](auto t) { r = int_launch<typename decltype(t)::type, true>(a, stream); });
+  return r;
 }

@@ -68,18 +68,18 @@ extern "C" int stj_softmax_fwd(const float* S, void* P, const int* qvalid, const
   const long long rows = batch * H * Nq;
   if (rows <= 0) return STJ_OK;
   const int grid = (int)((rows + 3) / 4 > 8192 ? 8192 : (rows + 3) / 4);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(softmax_fwd_kernel<bf16>, dim3(grid), dim3(256), 0, stream, S, (bf16*)P, qvalid, kvalid, bias, rows, H, Nq, Nk);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(softmax_fwd_kernel<f16>, dim3(grid), dim3(256), 0, stream, S, (f16*)P, qvalid, kvalid, bias, rows, H, Nq, Nk);
-  else hipLaunchKernelGGL(softmax_fwd_kernel<float>, dim3(grid), dim3(256), 0, stream, S, (float*)P, qvalid, kvalid, bias, rows, H, Nq, Nk);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(softmax_fwd_kernel<T>, dim3(grid), dim3(256), 0, stream, S, (T*)P, qvalid, kvalid, bias, rows, H, Nq, Nk);
+      })) { stj_set_error("stj_softmax_fwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_softmax_fwd");
 }
 extern "C" int stj_softmax_bwd(const void* P, const float* dP, void* dS, long long rows, int Nk, int dtype, hipStream_t stream) {
   if (Nk > 256 || Nk <= 0) { stj_set_error("softmax: Nk=%d unsupported (1..256)", Nk); return STJ_EUNSUPPORTED; }
   if (rows <= 0) return STJ_OK;
   const int grid = (int)((rows + 3) / 4 > 8192 ? 8192 : (rows + 3) / 4);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(softmax_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, stream, (const bf16*)P, dP, (bf16*)dS, rows, Nk);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(softmax_bwd_kernel<f16>, dim3(grid), dim3(256), 0, stream, (const f16*)P, dP, (f16*)dS, rows, Nk);
-  else hipLaunchKernelGGL(softmax_bwd_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)P, dP, (float*)dS, rows, Nk);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(softmax_bwd_kernel<T>, dim3(grid), dim3(256), 0, stream, (const T*)P, dP, (T*)dS, rows, Nk);
+      })) { stj_set_error("stj_softmax_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_softmax_bwd");
 }
 
@@ -194,7 +194,7 @@ __global__ __launch_bounds__(256) void small_attn_kernel(SmallAttnArgs a) {
   }
 }
 static size_t small_attn_lds(int N, int H, int d, int dtype, bool bwd) {
-  return (size_t)4 * H * N * N * 4 + (size_t)(bwd ? 4 : 3) * N * (H * d + 2) * (dtype == STJ_F32 ? 4 : 2);
+  return (size_t)4 * H * N * N * 4 + (size_t)(bwd ? 4 : 3) * N * (H * d + 2) * stj_elem_bytes(dtype);
 }
 // 1 when stj_small_attn_* take this geometry (else use stj_gemm + stj_softmax_* + stj_dropout)
 extern "C" int stj_small_attn_supported(int N, int H, int d, int dtype) {
@@ -205,10 +205,9 @@ template <bool BWD> static int small_attn_launch(const SmallAttnArgs& a, long lo
   if (!stj_small_attn_supported(a.N, a.H, a.d, dtype)) { stj_set_error("small_attn: N = %d, H = %d, d = %d not supported", a.N, a.H, a.d); return STJ_EUNSUPPORTED; }
   if (!(a.p_drop >= 0.f && a.p_drop < 1.f)) { stj_set_error("small_attn: need 0 <= p_drop < 1"); return STJ_EINVAL; }
   const size_t lds = small_attn_lds(a.N, a.H, a.d, dtype, BWD);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL((small_attn_kernel<bf16, BWD>), dim3((unsigned)Bt), dim3(256), lds, stream, a);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL((small_attn_kernel<f16, BWD>), dim3((unsigned)Bt), dim3(256), lds, stream, a);
-  else if (dtype == STJ_F32) hipLaunchKernelGGL((small_attn_kernel<float, BWD>), dim3((unsigned)Bt), dim3(256), lds, stream, a);
-  else { stj_set_error("small_attn: bad dtype %d", dtype); return STJ_EINVAL; }
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL((small_attn_kernel<T, BWD>), dim3((unsigned)Bt), dim3(256), lds, stream, a);
+      })) { stj_set_error("small_attn: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch(BWD ? "stj_small_attn_bwd" : "stj_small_attn_fwd");
 }
 // o [Bt,N,H*d] = dropout(softmax(scale q k^T + mask)) v per batch element and head; q, k, v [Bt,N,H*d]; qvalid / kvalid int32 [Bt,N] or NULL
@@ -473,7 +472,7 @@ __global__ __launch_bounds__(256) void fg_offset_bwd_kernel(const T* __restrict_
 }
 
 static int fgo_check(const char* who, int B, int HW, int G, int gc, int C2, int dtype, const void* p16a, const void* p16b) {
-  const int vn = dtype == STJ_F32 ? 4 : 8;
+  const int vn = stj_vec_elems(dtype);
   if (B < 1 || HW % 16 || G < 1 || G > 8 || gc < 1 || gc > 256 || C2 % vn || C2 / vn > 256) {
     stj_set_error("%s: unsupported geometry B=%d HW=%d G=%d gc=%d C2=%d", who, B, HW, G, gc, C2); return STJ_EINVAL;
   }
@@ -485,9 +484,9 @@ extern "C" int stj_fg_offset_fwd(const void* o, const void* W1, const void* W2, 
   if (int e = fgo_check("stj_fg_offset_fwd", B, HW, G, gc, C2, dtype, fh, qres)) return e;
   const size_t lds = (size_t)(3 * C2 + 32 * G) * sizeof(float);
   const int grid = B * (HW / 16);
-#define FGO_FWD(TT) hipLaunchKernelGGL(fg_offset_fwd_kernel<TT>, dim3(grid), dim3(256), lds, stream, (const TT*)o, (const TT*)W1, (const TT*)W2, b2, (const TT*)qres, (TT*)off, (TT*)fh, B, HW, G, gc, C2, scale, zmajor)
-  if (dtype == STJ_BF16) FGO_FWD(bf16); else if (dtype == STJ_F16) FGO_FWD(f16); else FGO_FWD(float);
-#undef FGO_FWD
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(fg_offset_fwd_kernel<T>, dim3(grid), dim3(256), lds, stream, (const T*)o, (const T*)W1, (const T*)W2, b2, (const T*)qres, (T*)off, (T*)fh, B, HW, G, gc, C2, scale, zmajor);
+      })) { stj_set_error("stj_fg_offset_fwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_fg_offset_fwd");
 }
 extern "C" int stj_fg_offset_bwd(const void* o, const void* off, const void* W1, const void* W2, const void* doff, const void* dfh,
@@ -496,9 +495,9 @@ extern "C" int stj_fg_offset_bwd(const void* o, const void* off, const void* W1,
   if (int e = fgo_check("stj_fg_offset_bwd", B, HW, G, gc, C2, dtype, dfh, dq)) return e;
   const size_t lds = (size_t)(5 * C2 + 64 * G + 4 * gc) * sizeof(float);
   const int grid = B * (HW / 16);
-#define FGO_BWD(TT) hipLaunchKernelGGL(fg_offset_bwd_kernel<TT>, dim3(grid), dim3(256), lds, stream, (const TT*)o, (const TT*)off, (const TT*)W1, (const TT*)W2, (const TT*)doff, (const TT*)dfh, (TT*)dO, (TT*)dq, (TT*)doff_out, dW1, dW2, db2, B, HW, G, gc, C2, scale, zmajor)
-  if (dtype == STJ_BF16) FGO_BWD(bf16); else if (dtype == STJ_F16) FGO_BWD(f16); else FGO_BWD(float);
-#undef FGO_BWD
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(fg_offset_bwd_kernel<T>, dim3(grid), dim3(256), lds, stream, (const T*)o, (const T*)off, (const T*)W1, (const T*)W2, (const T*)doff, (const T*)dfh, (T*)dO, (T*)dq, (T*)doff_out, dW1, dW2, db2, B, HW, G, gc, C2, scale, zmajor);
+      })) { stj_set_error("stj_fg_offset_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_fg_offset_bwd");
 }
 
@@ -506,9 +505,9 @@ extern "C" int stj_fg_bias_fwd(const void* off, const float* table, float* bias,
   const long long total = (long long)B * G * Hh * Ww * Hh * Ww;
   if (total <= 0) return STJ_OK;
   const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(fg_bias_fwd_kernel<bf16>, dim3(grid), dim3(256), 0, stream, (const bf16*)off, table, bias, B, G, Hh, Ww);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(fg_bias_fwd_kernel<f16>, dim3(grid), dim3(256), 0, stream, (const f16*)off, table, bias, B, G, Hh, Ww);
-  else hipLaunchKernelGGL(fg_bias_fwd_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)off, table, bias, B, G, Hh, Ww);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(fg_bias_fwd_kernel<T>, dim3(grid), dim3(256), 0, stream, (const T*)off, table, bias, B, G, Hh, Ww);
+      })) { stj_set_error("stj_fg_bias_fwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_fg_bias_fwd");
 }
 extern "C" int stj_fg_bias_bwd(const void* off, const float* table, const void* dbias, float* dtable, float* doff,
@@ -520,8 +519,8 @@ extern "C" int stj_fg_bias_bwd(const void* off, const float* table, const void* 
   if (QS > 8) QS = 8;
   const int grid = B * G * QS;
   const size_t lds = (size_t)(2 * Hh - 1) * (2 * Ww - 1) * 2 * sizeof(float);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(fg_bias_bwd_kernel<bf16>, dim3(grid), dim3(256), lds, stream, (const bf16*)off, table, (const bf16*)dbias, dtable, doff, B, G, Hh, Ww, QS);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(fg_bias_bwd_kernel<f16>, dim3(grid), dim3(256), lds, stream, (const f16*)off, table, (const f16*)dbias, dtable, doff, B, G, Hh, Ww, QS);
-  else hipLaunchKernelGGL(fg_bias_bwd_kernel<float>, dim3(grid), dim3(256), lds, stream, (const float*)off, table, (const float*)dbias, dtable, doff, B, G, Hh, Ww, QS);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(fg_bias_bwd_kernel<T>, dim3(grid), dim3(256), lds, stream, (const T*)off, table, (const T*)dbias, dtable, doff, B, G, Hh, Ww, QS);
+      })) { stj_set_error("stj_fg_bias_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_fg_bias_bwd");
 }

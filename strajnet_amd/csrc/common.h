@@ -315,8 +315,31 @@ __device__ __forceinline__ float pad_at(const float* img, int H, int W, int es, 
 // ---- host-side error plumbing -------------------------------------------------------------
 static inline bool stj_is16(int dtype) { return dtype == STJ_BF16 || dtype == STJ_F16; }
 static inline bool stj_dtype_ok(int dtype) { return dtype == STJ_F32 || dtype == STJ_BF16 || dtype == STJ_F16; }
+static inline int stj_elem_bytes(int dtype) { return stj_is16(dtype) ? 2 : 4; }
+static inline int stj_vec_elems(int dtype) { return 16 / stj_elem_bytes(dtype); }   // elements per 16 bytes: the host twin of Vec<T>::N
 void stj_set_error(const char* fmt, ...);
 int stj_check_launch(const char* what);
+bool stj_no_ws();   // STJ_NO_WS=1: the conv family's wave-specialised kernels are switched off (util.hip)
+
+// ---- run-time dtype code -> element type ---------------------------------------------------
+// A launcher calls its kernel once, inside a generic lambda: stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T; ... });
+// false = the code names no element type (nothing ran): the entry point refuses the call.
+template <typename T> struct DType { typedef T type; };
+template <typename F> static inline bool stj_with_dtype16(int dtype, F&& f) {   // the kernels that exist for the 16-bit types only
+  switch (dtype) {
+    case STJ_BF16: f(DType<bf16>{}); return true;
+    case STJ_F16: f(DType<f16>{}); return true;
+  }
+  return false;
+}
+template <typename F> static inline bool stj_with_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case STJ_BF16: f(DType<bf16>{}); return true;
+    case STJ_F16: f(DType<f16>{}); return true;
+    case STJ_F32: f(DType<float>{}); return true;
+  }
+  return false;
+}
 
 // A launcher's once-per-process state that is really once per DEVICE (hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the current
 // device's copy of the code object; the CU count is the current device's): one slot per device ordinal, read / written for the current one.

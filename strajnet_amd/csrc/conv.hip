@@ -445,9 +445,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 template <typename T>
 static bool upconv_dgrad_pf_try(const void* dP, const void* Wd, void* dX, const void* Xelu, int F, int Hi, int Wi, int Cin, int Cout, hipStream_t st) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("STJ_NO_WS"); on = !(e && atoi(e)); }      // STJ_NO_WS=1: generic conv kernels everywhere
-  if (!on || Hi % TILE_H || Wi % TILE_W || Cin % 64 || Cout % KC || Cin <= 128) return false;
+  if (stj_no_ws() || Hi % TILE_H || Wi % TILE_W || Cin % 64 || Cout % KC || Cin <= 128) return false;
   constexpr int FN = 4, BN = FN * 16, LDK = KC + 8;
   const size_t lds = (size_t)((2 * TILE_H + 2) * (2 * TILE_W + 2) * LDK + 16 * BN * LDK) * sizeof(T);
   static PerDevice<bool> attr_set;
@@ -568,9 +566,9 @@ __global__ __launch_bounds__(256) void upconv_wgrad_kernel(const T* X, const T* 
 // ---------------------------------------------------------------------------------------------------
 extern "C" int stj_upconv_prep(const float* W, void* Wf, void* Wd, int Cin, int Cout, int dtype, hipStream_t stream) {
   const int g = min(2048, (16 * Cin * Cout + 255) / 256);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(upconv_prep_kernel<bf16>, dim3(g), dim3(256), 0, stream, W, (bf16*)Wf, (bf16*)Wd, Cin, Cout);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(upconv_prep_kernel<f16>, dim3(g), dim3(256), 0, stream, W, (f16*)Wf, (f16*)Wd, Cin, Cout);
-  else hipLaunchKernelGGL(upconv_prep_kernel<float>, dim3(g), dim3(256), 0, stream, W, (float*)Wf, (float*)Wd, Cin, Cout);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(upconv_prep_kernel<T>, dim3(g), dim3(256), 0, stream, W, (T*)Wf, (T*)Wd, Cin, Cout);
+      })) { stj_set_error("stj_upconv_prep: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_upconv_prep");
 }
 extern "C" int stj_upconv_fold(const float* dWeff, float* dW, int Cin, int Cout, hipStream_t stream) {
@@ -580,7 +578,7 @@ extern "C" int stj_upconv_fold(const float* dWeff, float* dW, int Cin, int Cout,
 }
 
 static int upconv_check(int F, int Hi, int Wi, int Cin, int Cout, int dtype) {
-  const int vn = stj_is16(dtype) ? 8 : 4;
+  const int vn = stj_vec_elems(dtype);
   if (F <= 0 || Hi <= 0 || Wi <= 0) { stj_set_error("upconv: empty problem"); return STJ_EINVAL; }
   if (Cin % vn || Cout % vn) { stj_set_error("upconv: channels must be multiples of %d (Cin=%d Cout=%d)", vn, Cin, Cout); return STJ_EINVAL; }
   return STJ_OK;
@@ -607,11 +605,7 @@ bool outconv_bwd_mfma_try(const void* X, const float* W, const float* dY, void* 
                           int Tn, long long y_bs, long long y_ts, long long y_ps, int elu_in, void* ws, long long ws_bytes, hipStream_t st);
 long long outconv_bwd_ws_bytes();
 bool upconv_dgrad_ws_try(const void* dP, const void* Wd, void* dX, const void* Xelu, int F, int Hi, int Wi, int Cin, int Cout, hipStream_t st);
-static bool ws_enabled() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("STJ_NO_WS"); v = (e && e[0] == '1') ? 0 : 1; }
-  return v == 1;
-}
+static bool ws_enabled() { return !stj_no_ws(); }
 extern "C" int stj_upconv_fwd(const void* X, const void* Wf, const float* bias, void* Y, int F, int Hi, int Wi, int Cin,
                               int Cout, int act, int dtype, hipStream_t stream) {
   int e = upconv_check(F, Hi, Wi, Cin, Cout, dtype);
@@ -620,9 +614,9 @@ extern "C" int stj_upconv_fwd(const void* X, const void* Wf, const float* bias, 
     return stj_check_launch("stj_upconv_fwd(ws)");
   if (stj_is16(dtype) && ws_enabled() && upconv_fwd_ps_try(X, Wf, bias, Y, F, Hi, Wi, Cin, Cout, act, dtype, stream))
     return stj_check_launch("stj_upconv_fwd(ps)");
-  if (dtype == STJ_F16) return upconv_fwd_launch<f16>(X, Wf, bias, Y, F, Hi, Wi, Cin, Cout, act, stream);
-  return dtype == STJ_BF16 ? upconv_fwd_launch<bf16>(X, Wf, bias, Y, F, Hi, Wi, Cin, Cout, act, stream)
-                           : upconv_fwd_launch<float>(X, Wf, bias, Y, F, Hi, Wi, Cin, Cout, act, stream);
+  int r = STJ_EINVAL;
+  if (!stj_with_dtype(dtype, [&](auto t) { r = upconv_fwd_launch<typename decltype(t)::type>(X, Wf, bias, Y, F, Hi, Wi, Cin, Cout, act, stream); })) stj_set_error("stj_upconv_fwd: bad dtype %d", dtype);
+  return r;
 }
 
 // Up-conv with the decoder's skip sums in its epilogue: Y = ELU(conv(up(X)) + bias) + R1 and (optional) Y2 = Y + R2, all [F,2Hi,2Wi,Cout]
@@ -657,11 +651,12 @@ extern "C" int stj_upconv_dgrad(const void* dP, const void* Wd, void* dX, const 
   if (e) return e;
   if (dtype == STJ_BF16 && ws_enabled() && upconv_dgrad_ws_try(dP, Wd, dX, Xelu, F, Hi, Wi, Cin, Cout, stream))
     return stj_check_launch("stj_upconv_dgrad(ws)");
-  if (dtype == STJ_BF16 && upconv_dgrad_pf_try<bf16>(dP, Wd, dX, Xelu, F, Hi, Wi, Cin, Cout, stream)) return stj_check_launch("stj_upconv_dgrad(pf)");
-  if (dtype == STJ_F16 && upconv_dgrad_pf_try<f16>(dP, Wd, dX, Xelu, F, Hi, Wi, Cin, Cout, stream)) return stj_check_launch("stj_upconv_dgrad(pf)");
-  if (dtype == STJ_F16) return upconv_dgrad_launch<f16>(dP, Wd, dX, Xelu, F, Hi, Wi, Cin, Cout, stream);
-  return dtype == STJ_BF16 ? upconv_dgrad_launch<bf16>(dP, Wd, dX, Xelu, F, Hi, Wi, Cin, Cout, stream)
-                           : upconv_dgrad_launch<float>(dP, Wd, dX, Xelu, F, Hi, Wi, Cin, Cout, stream);
+  bool pf = false;
+  stj_with_dtype16(dtype, [&](auto t) { pf = upconv_dgrad_pf_try<typename decltype(t)::type>(dP, Wd, dX, Xelu, F, Hi, Wi, Cin, Cout, stream); });
+  if (pf) return stj_check_launch("stj_upconv_dgrad(pf)");
+  int r = STJ_EINVAL;
+  if (!stj_with_dtype(dtype, [&](auto t) { r = upconv_dgrad_launch<typename decltype(t)::type>(dP, Wd, dX, Xelu, F, Hi, Wi, Cin, Cout, stream); })) stj_set_error("stj_upconv_dgrad: bad dtype %d", dtype);
+  return r;
 }
 
 template <typename T>
@@ -696,9 +691,9 @@ extern "C" int stj_upconv_wgrad(const void* X, const void* dP, float* dWeff, flo
   if (db_parts < 1) db_parts = 1;
   if (dtype == STJ_BF16 && ws_enabled() && upconv_wgrad_tr_try(X, dP, dWeff, dbias, db_parts, F, Hi, Wi, Cin, Cout, wg_budget, stream))
     return stj_check_launch("stj_upconv_wgrad(tr)");
-  if (dtype == STJ_F16) return upconv_wgrad_launch<f16>(X, dP, dWeff, dbias, db_parts, F, Hi, Wi, Cin, Cout, stream);
-  return dtype == STJ_BF16 ? upconv_wgrad_launch<bf16>(X, dP, dWeff, dbias, db_parts, F, Hi, Wi, Cin, Cout, stream)
-                           : upconv_wgrad_launch<float>(X, dP, dWeff, dbias, db_parts, F, Hi, Wi, Cin, Cout, stream);
+  int r = STJ_EINVAL;
+  if (!stj_with_dtype(dtype, [&](auto t) { r = upconv_wgrad_launch<typename decltype(t)::type>(X, dP, dWeff, dbias, db_parts, F, Hi, Wi, Cin, Cout, stream); })) stj_set_error("stj_upconv_wgrad: bad dtype %d", dtype);
+  return r;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -860,16 +855,10 @@ extern "C" int stj_outconv_fwd(const void* X, const float* W, const float* bias,
   const size_t lds = (size_t)(18 * 18 * (C + 1) + 9 * C * 2) * 4;
   if (lds > 160 * 1024) { stj_set_error("outconv: C=%d too large for LDS", C); return STJ_EUNSUPPORTED; }
   const int grid = F * (Hh / OC_T) * (Ww / OC_T);
-  if (dtype == STJ_BF16) {
-    hipFuncSetAttribute((const void*)outconv_fwd_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(outconv_fwd_kernel<bf16>, dim3(grid), dim3(256), lds, stream, (const bf16*)X, W, bias, Y, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride);
-  } else if (dtype == STJ_F16) {
-    hipFuncSetAttribute((const void*)outconv_fwd_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(outconv_fwd_kernel<f16>, dim3(grid), dim3(256), lds, stream, (const f16*)X, W, bias, Y, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride);
-  } else {
-    hipFuncSetAttribute((const void*)outconv_fwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(outconv_fwd_kernel<float>, dim3(grid), dim3(256), lds, stream, (const float*)X, W, bias, Y, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride);
-  }
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipFuncSetAttribute((const void*)outconv_fwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(outconv_fwd_kernel<T>, dim3(grid), dim3(256), lds, stream, (const T*)X, W, bias, Y, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride);
+      })) { stj_set_error("stj_outconv_fwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_outconv_fwd");
 }
 // Both heads of the model output in one launch: Y [B,H,W,4*Tn] f32, channel 4 t + 2 head + o; X0 / X1 the two 48-channel decoder
@@ -937,16 +926,10 @@ extern "C" int stj_outconv_bwd(const void* X, const float* W, const float* dY, v
   const size_t lds = (size_t)(18 * 18 * (C + 1) + 9 * C * 2 + 18 * 18 * 2) * 4;
   if (lds > 160 * 1024 || 9 * C > 1024) { stj_set_error("outconv: C=%d too large", C); return STJ_EUNSUPPORTED; }
   const int grid = min(1024, F * (Hh / OC_T) * (Ww / OC_T));
-  if (dtype == STJ_BF16) {
-    hipFuncSetAttribute((const void*)outconv_bwd_kernel<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(outconv_bwd_kernel<bf16>, dim3(grid), dim3(256), lds, stream, (const bf16*)X, W, dY, (bf16*)dX, dW, db, F, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride, elu_in);
-  } else if (dtype == STJ_F16) {
-    hipFuncSetAttribute((const void*)outconv_bwd_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(outconv_bwd_kernel<f16>, dim3(grid), dim3(256), lds, stream, (const f16*)X, W, dY, (f16*)dX, dW, db, F, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride, elu_in);
-  } else {
-    hipFuncSetAttribute((const void*)outconv_bwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(outconv_bwd_kernel<float>, dim3(grid), dim3(256), lds, stream, (const float*)X, W, dY, (float*)dX, dW, db, F, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride, elu_in);
-  }
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipFuncSetAttribute((const void*)outconv_bwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(outconv_bwd_kernel<T>, dim3(grid), dim3(256), lds, stream, (const T*)X, W, dY, (T*)dX, dW, db, F, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride, elu_in);
+      })) { stj_set_error("stj_outconv_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_outconv_bwd");
 }
 
@@ -972,9 +955,9 @@ extern "C" int stj_im2col_patch(const float* src, void* dst, int B, int H, int W
   const long long total = (long long)B * (H / 4) * (W / 4) * 16 * Cin;
   if (total <= 0) return STJ_OK;
   const int g = (int)min(8192ll, (total + 255) / 256);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(im2col_patch_kernel<bf16>, dim3(g), dim3(256), 0, stream, src, (bf16*)dst, B, H, W, Cin, pix_stride, ch_stride);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(im2col_patch_kernel<f16>, dim3(g), dim3(256), 0, stream, src, (f16*)dst, B, H, W, Cin, pix_stride, ch_stride);
-  else hipLaunchKernelGGL(im2col_patch_kernel<float>, dim3(g), dim3(256), 0, stream, src, (float*)dst, B, H, W, Cin, pix_stride, ch_stride);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(im2col_patch_kernel<T>, dim3(g), dim3(256), 0, stream, src, (T*)dst, B, H, W, Cin, pix_stride, ch_stride);
+      })) { stj_set_error("stj_im2col_patch: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_im2col_patch");
 }
 
@@ -1060,34 +1043,34 @@ __global__ __launch_bounds__(256) void col2im3_kernel(const T* dcols, T* dx, int
 extern "C" int stj_im2col3(const void* x, void* cols, int N, int H, int W, int G, int Cg, int dtype, hipStream_t stream) {
   const long long total = (long long)N * H * W * G * 9 * Cg;
   if (total <= 0) return STJ_OK;
-  const int vn = dtype == STJ_F32 ? 4 : 8;
+  const int vn = stj_vec_elems(dtype);
   if (Cg % vn == 0 && total < (1ll << 31) && !((((uintptr_t)x) | ((uintptr_t)cols)) & 15)) {
     const int gv = (int)min(8192ll, (total / vn + 255) / 256);
-    if (dtype == STJ_BF16) hipLaunchKernelGGL(im2col3_vec_kernel<bf16>, dim3(gv), dim3(256), 0, stream, (const bf16*)x, (bf16*)cols, N, H, W, G, Cg);
-    else if (dtype == STJ_F16) hipLaunchKernelGGL(im2col3_vec_kernel<f16>, dim3(gv), dim3(256), 0, stream, (const f16*)x, (f16*)cols, N, H, W, G, Cg);
-    else hipLaunchKernelGGL(im2col3_vec_kernel<float>, dim3(gv), dim3(256), 0, stream, (const float*)x, (float*)cols, N, H, W, G, Cg);
+    if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+          hipLaunchKernelGGL(im2col3_vec_kernel<T>, dim3(gv), dim3(256), 0, stream, (const T*)x, (T*)cols, N, H, W, G, Cg);
+        })) { stj_set_error("stj_im2col3: bad dtype %d", dtype); return STJ_EINVAL; }
     return stj_check_launch("stj_im2col3");
   }
   const int g = (int)min(8192ll, (total + 255) / 256);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(im2col3_kernel<bf16>, dim3(g), dim3(256), 0, stream, (const bf16*)x, (bf16*)cols, N, H, W, G, Cg);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(im2col3_kernel<f16>, dim3(g), dim3(256), 0, stream, (const f16*)x, (f16*)cols, N, H, W, G, Cg);
-  else hipLaunchKernelGGL(im2col3_kernel<float>, dim3(g), dim3(256), 0, stream, (const float*)x, (float*)cols, N, H, W, G, Cg);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(im2col3_kernel<T>, dim3(g), dim3(256), 0, stream, (const T*)x, (T*)cols, N, H, W, G, Cg);
+      })) { stj_set_error("stj_im2col3: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_im2col3");
 }
 extern "C" int stj_col2im3(const void* dcols, void* dx, int N, int H, int W, int G, int Cg, int dtype, hipStream_t stream) {
   const long long total = (long long)N * H * W * G * Cg;
   if (total <= 0) return STJ_OK;
-  const int vn = dtype == STJ_F32 ? 4 : 8;
+  const int vn = stj_vec_elems(dtype);
   if (Cg % vn == 0 && total * 9 < (1ll << 31) && !((((uintptr_t)dcols) | ((uintptr_t)dx)) & 15)) {
     const int gv = (int)min(8192ll, (total / vn + 255) / 256);
-    if (dtype == STJ_BF16) hipLaunchKernelGGL(col2im3_vec_kernel<bf16>, dim3(gv), dim3(256), 0, stream, (const bf16*)dcols, (bf16*)dx, N, H, W, G, Cg);
-    else if (dtype == STJ_F16) hipLaunchKernelGGL(col2im3_vec_kernel<f16>, dim3(gv), dim3(256), 0, stream, (const f16*)dcols, (f16*)dx, N, H, W, G, Cg);
-    else hipLaunchKernelGGL(col2im3_vec_kernel<float>, dim3(gv), dim3(256), 0, stream, (const float*)dcols, (float*)dx, N, H, W, G, Cg);
+    if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+          hipLaunchKernelGGL(col2im3_vec_kernel<T>, dim3(gv), dim3(256), 0, stream, (const T*)dcols, (T*)dx, N, H, W, G, Cg);
+        })) { stj_set_error("stj_col2im3: bad dtype %d", dtype); return STJ_EINVAL; }
     return stj_check_launch("stj_col2im3");
   }
   const int g = (int)min(8192ll, (total + 255) / 256);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(col2im3_kernel<bf16>, dim3(g), dim3(256), 0, stream, (const bf16*)dcols, (bf16*)dx, N, H, W, G, Cg);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(col2im3_kernel<f16>, dim3(g), dim3(256), 0, stream, (const f16*)dcols, (f16*)dx, N, H, W, G, Cg);
-  else hipLaunchKernelGGL(col2im3_kernel<float>, dim3(g), dim3(256), 0, stream, (const float*)dcols, (float*)dx, N, H, W, G, Cg);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(col2im3_kernel<T>, dim3(g), dim3(256), 0, stream, (const T*)dcols, (T*)dx, N, H, W, G, Cg);
+      })) { stj_set_error("stj_col2im3: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_col2im3");
 }

@@ -233,16 +233,14 @@ static bool fwd_ps_try_t(const void* X, const void* Wf, const float* bias, void*
 // true when this kernel took the problem: 16-bit, ELU, Cin a multiple of 32 above the weight-stationary range
 bool upconv_fwd_ps_try(const void* X, const void* Wf, const float* bias, void* Y, int F, int Hi, int Wi, int Cin, int Cout, int act,
                        int dtype, hipStream_t st) {
-  static int on = -1;
-  if (on < 0) { const char* e = getenv("STJ_NO_WS"); on = !(e && atoi(e)); }      // STJ_NO_WS=1: generic conv kernels everywhere
-  if (!on || act != ACT_ELU || Cin % PS_KC || Cin <= 128 || Cout % 32) return false;
-  return dtype == STJ_F16 ? fwd_ps_try_t<f16>(X, Wf, bias, Y, nullptr, nullptr, nullptr, F, Hi, Wi, Cin, Cout, st)
-                          : fwd_ps_try_t<bf16>(X, Wf, bias, Y, nullptr, nullptr, nullptr, F, Hi, Wi, Cin, Cout, st);
+  if (stj_no_ws() || act != ACT_ELU || Cin % PS_KC || Cin <= 128 || Cout % 32) return false;
+  bool took = false;
+  return stj_with_dtype16(dtype, [&](auto t) { took = fwd_ps_try_t<typename decltype(t)::type>(X, Wf, bias, Y, nullptr, nullptr, nullptr, F, Hi, Wi, Cin, Cout, st); }) && took;
 }
 // the same with the skip sums in the epilogue: Y = ELU(conv) + R1, Y2 = Y + R2 (Y2 / R2 may be null)
 bool upconv_fwd_ps_res_try(const void* X, const void* Wf, const float* bias, void* Y, const void* R1, void* Y2, const void* R2, int F, int Hi,
                            int Wi, int Cin, int Cout, int dtype, hipStream_t st) {
   if (Cin % PS_KC || Cin <= 128 || Cout % 32 || R1 == nullptr || ((Y2 == nullptr) != (R2 == nullptr))) return false;
-  return dtype == STJ_F16 ? fwd_ps_try_t<f16>(X, Wf, bias, Y, R1, Y2, R2, F, Hi, Wi, Cin, Cout, st)
-                          : fwd_ps_try_t<bf16>(X, Wf, bias, Y, R1, Y2, R2, F, Hi, Wi, Cin, Cout, st);
+  bool took = false;
+  return stj_with_dtype16(dtype, [&](auto t) { took = fwd_ps_try_t<typename decltype(t)::type>(X, Wf, bias, Y, R1, Y2, R2, F, Hi, Wi, Cin, Cout, st); }) && took;
 }

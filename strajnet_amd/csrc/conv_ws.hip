@@ -431,7 +431,8 @@ static bool ws2_head_launch(const void* X, const void* Wf, const float* bias, co
 bool upconv_fwd_head_try(const void* X, const void* Wf, const float* bias, const float* Wh, void* Z, int F, int Hi, int Wi, int Cin, int Cout, int dtype,
                          hipStream_t st) {
   if (Cin != 96 || Cout != 48 || Hi % WS_TH || Wi % WS_TW) return false;
-  return dtype == STJ_F16 ? ws2_head_launch<f16>(X, Wf, bias, Wh, Z, F, Hi, Wi, st) : ws2_head_launch<bf16>(X, Wf, bias, Wh, Z, F, Hi, Wi, st);
+  bool took = false;
+  return stj_with_dtype16(dtype, [&](auto t) { took = ws2_head_launch<typename decltype(t)::type>(X, Wf, bias, Wh, Z, F, Hi, Wi, st); }) && took;
 }
 template <typename T, int KS, int NF>
 static bool ws2_launch(const void* X, const void* Wf, const float* bias, void* Y, int F, int Hi, int Wi, int Cout, hipStream_t st) {
@@ -458,8 +459,8 @@ static bool upconv_fwd_ws_try_t(const void* X, const void* Wf, const float* bias
 }
 bool upconv_fwd_ws_try(const void* X, const void* Wf, const float* bias, void* Y, int F, int Hi, int Wi, int Cin, int Cout, int act,
                        int dtype, hipStream_t st) {
-  return dtype == STJ_F16 ? upconv_fwd_ws_try_t<f16>(X, Wf, bias, Y, F, Hi, Wi, Cin, Cout, act, st)
-                          : upconv_fwd_ws_try_t<bf16>(X, Wf, bias, Y, F, Hi, Wi, Cin, Cout, act, st);
+  bool took = false;
+  return stj_with_dtype16(dtype, [&](auto t) { took = upconv_fwd_ws_try_t<typename decltype(t)::type>(X, Wf, bias, Y, F, Hi, Wi, Cin, Cout, act, st); }) && took;
 }
 
 // =====================================================================================================
@@ -1122,11 +1123,9 @@ bool outconv_pair_fwd_try(const void* X0, const void* X1, const float* W0, const
   // (one / two spatial tiles per workgroup instead of four, i.e. 2048 / 1024 shorter-lived workgroups: 187-193 / 172-179 us against 172-175 in a hot loop)
   const int per = (nsp + 256 * OCP_MINB - 1) / (256 * OCP_MINB);
   const int nb = (nsp + per - 1) / per;
-  if (dtype == STJ_F16)
-    hipLaunchKernelGGL((outconv_pair_fwd_kernel<f16, 48>), dim3(nb), dim3(256), 0, st, (const f16*)X0, (const f16*)X1, W0, W1, b0, b1, Y, B, Hh, Ww, t_major, nsp);
-  else
-    hipLaunchKernelGGL((outconv_pair_fwd_kernel<bf16, 48>), dim3(nb), dim3(256), 0, st, (const bf16*)X0, (const bf16*)X1, W0, W1, b0, b1, Y, B, Hh, Ww, t_major, nsp);
-  return true;
+  return stj_with_dtype16(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((outconv_pair_fwd_kernel<T, 48>), dim3(nb), dim3(256), 0, st, (const T*)X0, (const T*)X1, W0, W1, b0, b1, Y, B, Hh, Ww, t_major, nsp);
+  });
 }
 
 // Second half of the inference heads (first half: the HEAD epilogue of upconv_fwd_ws2_kernel): Y[b, y, x, 4 t + 2 h + o] = bias_h[o] +
@@ -1235,11 +1234,9 @@ static bool outconv_pair_gather_launch(const void* Z0, const void* Z1, const flo
   if (Tn != 8 || Hh % OCM_T || Ww % OCM_T || (((uintptr_t)Y | (uintptr_t)Z0 | (uintptr_t)Z1) & 15)) return false;
   const int nsp = B * (Hh / OCM_T) * (Ww / OCM_T);
   const int nb = nsp < 2048 ? nsp : 2048;
-  if (dtype == STJ_F16)
-    hipLaunchKernelGGL((outconv_pair_gather_kernel<f16, QUANT>), dim3(nb), dim3(256), 0, st, (const f16*)Z0, (const f16*)Z1, b0, b1, Y, B, Hh, Ww, t_major, nsp);
-  else
-    hipLaunchKernelGGL((outconv_pair_gather_kernel<bf16, QUANT>), dim3(nb), dim3(256), 0, st, (const bf16*)Z0, (const bf16*)Z1, b0, b1, Y, B, Hh, Ww, t_major, nsp);
-  return true;
+  return stj_with_dtype16(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((outconv_pair_gather_kernel<T, QUANT>), dim3(nb), dim3(256), 0, st, (const T*)Z0, (const T*)Z1, b0, b1, Y, B, Hh, Ww, t_major, nsp);
+  });
 }
 bool outconv_pair_gather_try(const void* Z0, const void* Z1, const float* b0, const float* b1, float* Y, int B, int Tn, int Hh, int Ww, int t_major,
                              int dtype, hipStream_t st) {
@@ -1469,11 +1466,9 @@ bool outconv_fwd_mfma_try(const void* X, const float* W, const float* bias, floa
   const int ntiles = F * (Hh / OCM_T) * (Ww / OCM_T);
   const int dbg = 0, nbm = 768;
   const int nb = min(ntiles, nbm);
-  if (dtype == STJ_F16)
-    hipLaunchKernelGGL((outconv_fwd_mfma2_kernel<f16, 48>), dim3(nb), dim3(256), 0, st, (const f16*)X, W, bias, Y, F, Hh, Ww, Tn, y_bs, y_ts, y_ps, dbg);
-  else
-    hipLaunchKernelGGL((outconv_fwd_mfma2_kernel<bf16, 48>), dim3(nb), dim3(256), 0, st, (const bf16*)X, W, bias, Y, F, Hh, Ww, Tn, y_bs, y_ts, y_ps, dbg);
-  return true;
+  return stj_with_dtype16(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL((outconv_fwd_mfma2_kernel<T, 48>), dim3(nb), dim3(256), 0, st, (const T*)X, W, bias, Y, F, Hh, Ww, Tn, y_bs, y_ts, y_ps, dbg);
+  });
 }
 long long outconv_bwd_ws_bytes() { return (long long)OCB_MAXBLK * OCB_PART * sizeof(float); }
 bool outconv_bwd_mfma_try(const void* X, const float* W, const float* dY, void* dX, float* dW, float* db, int F, int Hh, int Ww, int C,

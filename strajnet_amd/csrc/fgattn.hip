@@ -433,7 +433,9 @@ extern "C" int stj_fg_attn_fwd(const void* q, const void* k, const void* v, cons
   if (c) return c > 0 ? STJ_OK : c;
   fga::Args p = {};
   p.q = q; p.k = k; p.v = v; p.off = off; p.table = table; p.a = a; p.lse = lse; p.B = B; p.G = G; p.Hh = Hh; p.Ww = Ww; p.scale = scale;
-  return dtype == STJ_BF16 ? fga::dispatch<bf16>(false, p, stream) : (dtype == STJ_F16 ? fga::dispatch<f16>(false, p, stream) : fga::dispatch<float>(false, p, stream));
+  int rc = STJ_EINVAL;      // (fga::check: a known dtype)
+  stj_with_dtype(dtype, [&](auto t) { rc = fga::dispatch<typename decltype(t)::type>(false, p, stream); });
+  return rc;
 }
 // bytes of each of the two partial-sum workspaces (dkp, dvp) of stj_fg_attn_bwd
 extern "C" long long stj_fg_attn_bwd_workspace_bytes(int B, int G, int Hh, int Ww) {
@@ -452,15 +454,15 @@ extern "C" int stj_fg_attn_bwd(const void* q, const void* k, const void* v, cons
   p.q = q; p.k = k; p.v = v; p.off = off; p.table = table; p.a = const_cast<void*>(a); p.lse = const_cast<float*>(lse); p.da = da; p.dq = dq;
   p.dkp = dkp; p.dvp = dvp; p.dtable = dtable; p.doff = doff;
   p.B = B; p.G = G; p.Hh = Hh; p.Ww = Ww; p.scale = scale;
-  int rc = dtype == STJ_BF16 ? fga::dispatch<bf16>(true, p, stream) : (dtype == STJ_F16 ? fga::dispatch<f16>(true, p, stream) : fga::dispatch<float>(true, p, stream));
+  int rc = STJ_EINVAL;      // (fga::check: a known dtype)
+  stj_with_dtype(dtype, [&](auto t) { rc = fga::dispatch<typename decltype(t)::type>(true, p, stream); });
   if (rc != STJ_OK) return rc;
   const int HW = Hh * Ww;
-  const int tq = Hh == 16 ? (dtype == STJ_F32 ? fga::Split<16, true, float>::TQ : fga::Split<16, true, bf16>::TQ) : fga::Split<4, true, bf16>::TQ;
-  const int tiles = HW / tq;
   const long long n = 2ll * B * HW * G * fga::D;
   const int grid = (int)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(fga::fgattn_dkv_reduce_kernel<bf16>, dim3(grid), dim3(256), 0, stream, dkp, dvp, (bf16*)dk, (bf16*)dv, B, G, HW, tiles);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(fga::fgattn_dkv_reduce_kernel<f16>, dim3(grid), dim3(256), 0, stream, dkp, dvp, (f16*)dk, (f16*)dv, B, G, HW, tiles);
-  else hipLaunchKernelGGL(fga::fgattn_dkv_reduce_kernel<float>, dim3(grid), dim3(256), 0, stream, dkp, dvp, (float*)dk, (float*)dv, B, G, HW, tiles);
+  stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+    const int tiles = HW / (Hh == 16 ? fga::Split<16, true, T>::TQ : fga::Split<4, true, T>::TQ);      // query tiles of the backward kernel
+    hipLaunchKernelGGL(fga::fgattn_dkv_reduce_kernel<T>, dim3(grid), dim3(256), 0, stream, dkp, dvp, (T*)dk, (T*)dv, B, G, HW, tiles);
+  });
   return stj_check_launch("stj_fg_attn_dkv_reduce");
 }

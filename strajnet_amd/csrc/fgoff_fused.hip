@@ -332,16 +332,15 @@ extern "C" int stj_fgoff_supported(int H, int W, int C, int G, int dtype) {
 static long long fgoff_pack_elems(int dtype) { return 2 * (stj_is16(dtype) ? fgo::FG<bf16>::DIR : fgo::FG<float>::DIR); }
 extern "C" long long stj_fgoff_pack_workspace_bytes(int dtype) {
   if (!stj_dtype_ok(dtype)) return 0;
-  return fgoff_pack_elems(dtype) * (stj_is16(dtype) ? 2 : 4);
+  return fgoff_pack_elems(dtype) * stj_elem_bytes(dtype);
 }
 extern "C" int stj_fgoff_pack(const float* w, void* out, int dtype, hipStream_t stream) {
   if (!w || !out) { stj_set_error("stj_fgoff_pack: null pointer"); return STJ_EINVAL; }
-  if (!stj_dtype_ok(dtype)) { stj_set_error("stj_fgoff_pack: bad dtype %d", dtype); return STJ_EINVAL; }
   if ((uintptr_t)out & 15) { stj_set_error("stj_fgoff_pack: out must be 16-byte aligned"); return STJ_EINVAL; }
   const int grid = (int)((fgoff_pack_elems(dtype) + 255) / 256);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(fgo::fgoff_pack_kernel<bf16>, dim3(grid), dim3(256), 0, stream, w, (bf16*)out);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(fgo::fgoff_pack_kernel<f16>, dim3(grid), dim3(256), 0, stream, w, (f16*)out);
-  else hipLaunchKernelGGL(fgo::fgoff_pack_kernel<float>, dim3(grid), dim3(256), 0, stream, w, (float*)out);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(fgo::fgoff_pack_kernel<T>, dim3(grid), dim3(256), 0, stream, w, (T*)out);
+      })) { stj_set_error("stj_fgoff_pack: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_fgoff_pack");
 }
 
@@ -383,11 +382,9 @@ template <bool BWD> static int fgoff_run(const stj_fgoff_args* s, hipStream_t st
   a.off = s->off; a.cols = s->cols; a.c = s->c; a.mean = s->mean; a.rstd = s->rstd;
   a.doff = s->doff; a.dc = s->dc; a.dq = s->dq; a.d_w1 = s->d_w1; a.d_gamma = s->d_gamma; a.d_beta = s->d_beta; a.d_bias = s->d_bias;
   const int R = fgoff_rows(s->H, s->W, s->dtype, s->B);
-#define FGOFF_GO(WW, RR)                                                              \
-  if (s->W == WW && R == RR) {                                                        \
-    if (s->dtype == STJ_BF16) return fgoff_launch<bf16, WW, RR, BWD>(a, stream);      \
-    if (s->dtype == STJ_F16) return fgoff_launch<f16, WW, RR, BWD>(a, stream);        \
-  }
+  int r = STJ_OK;
+#define FGOFF_GO(WW, RR)      /* the 16-bit row geometries (f32: the two below) */                                                        \
+  if (s->W == WW && R == RR && stj_with_dtype16(s->dtype, [&](auto t) { r = fgoff_launch<typename decltype(t)::type, WW, RR, BWD>(a, stream); })) return r;
   FGOFF_GO(8, 2) FGOFF_GO(16, 1) FGOFF_GO(16, 2) FGOFF_GO(32, 1)
 #undef FGOFF_GO
   if (s->W == 8) return fgoff_launch<float, 8, 2, BWD>(a, stream);

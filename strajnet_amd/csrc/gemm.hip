@@ -573,41 +573,37 @@ static int group_flush(GroupState* gs, hipStream_t st) {
     const int c = g.cfg[0] & 7, deep1 = g.cfg[0] & 8;
     dim3 grid(g.gx[0], g.gy[0]);
     if (deep1) {
-#define STJ_ONE_DEEP(T) \
-      switch (c) { \
-        case 0: hipLaunchKernelGGL((gemm_deepk_kernel<T, 64, 64, false, false>), grid, dim3(256), 0, st, g.p[0]); break; \
-        case 1: hipLaunchKernelGGL((gemm_deepk_kernel<T, 64, 64, false, true>), grid, dim3(256), 0, st, g.p[0]); break; \
-        case 2: hipLaunchKernelGGL((gemm_deepk_kernel<T, 64, 64, true, false>), grid, dim3(256), 0, st, g.p[0]); break; \
-        case 3: hipLaunchKernelGGL((gemm_deepk_kernel<T, 64, 64, true, true>), grid, dim3(256), 0, st, g.p[0]); break; \
-        case 4: hipLaunchKernelGGL((gemm_deepk_kernel<T, 32, 32, false, false>), grid, dim3(256), 0, st, g.p[0]); break; \
-        case 5: hipLaunchKernelGGL((gemm_deepk_kernel<T, 32, 32, false, true>), grid, dim3(256), 0, st, g.p[0]); break; \
-        case 6: hipLaunchKernelGGL((gemm_deepk_kernel<T, 32, 32, true, false>), grid, dim3(256), 0, st, g.p[0]); break; \
-        default: hipLaunchKernelGGL((gemm_deepk_kernel<T, 32, 32, true, true>), grid, dim3(256), 0, st, g.p[0]); break; \
-      }
-      if (dtype == STJ_BF16) { STJ_ONE_DEEP(bf16) } else { STJ_ONE_DEEP(f16) }
-#undef STJ_ONE_DEEP
+      stj_with_dtype16(dtype, [&](auto t) { typedef typename decltype(t)::type T;      // (deep k-tile bodies are recorded for the 16-bit types only)
+        switch (c) {
+          case 0: hipLaunchKernelGGL((gemm_deepk_kernel<T, 64, 64, false, false>), grid, dim3(256), 0, st, g.p[0]); break;
+          case 1: hipLaunchKernelGGL((gemm_deepk_kernel<T, 64, 64, false, true>), grid, dim3(256), 0, st, g.p[0]); break;
+          case 2: hipLaunchKernelGGL((gemm_deepk_kernel<T, 64, 64, true, false>), grid, dim3(256), 0, st, g.p[0]); break;
+          case 3: hipLaunchKernelGGL((gemm_deepk_kernel<T, 64, 64, true, true>), grid, dim3(256), 0, st, g.p[0]); break;
+          case 4: hipLaunchKernelGGL((gemm_deepk_kernel<T, 32, 32, false, false>), grid, dim3(256), 0, st, g.p[0]); break;
+          case 5: hipLaunchKernelGGL((gemm_deepk_kernel<T, 32, 32, false, true>), grid, dim3(256), 0, st, g.p[0]); break;
+          case 6: hipLaunchKernelGGL((gemm_deepk_kernel<T, 32, 32, true, false>), grid, dim3(256), 0, st, g.p[0]); break;
+          default: hipLaunchKernelGGL((gemm_deepk_kernel<T, 32, 32, true, true>), grid, dim3(256), 0, st, g.p[0]); break;
+        }
+      });
       return stj_check_launch("stj_gemm(group of 1, deep k)");
     }
-#define STJ_ONE(T) \
-    switch (c) { \
-      case 0: hipLaunchKernelGGL((gemm_kernel<T, 64, 64, 2, 2, false, false>), grid, dim3(256), 0, st, g.p[0]); break; \
-      case 1: hipLaunchKernelGGL((gemm_kernel<T, 64, 64, 2, 2, false, true>), grid, dim3(256), 0, st, g.p[0]); break; \
-      case 2: hipLaunchKernelGGL((gemm_kernel<T, 64, 64, 2, 2, true, false>), grid, dim3(256), 0, st, g.p[0]); break; \
-      case 3: hipLaunchKernelGGL((gemm_kernel<T, 64, 64, 2, 2, true, true>), grid, dim3(256), 0, st, g.p[0]); break; \
-      case 4: hipLaunchKernelGGL((gemm_kernel<T, 32, 32, 2, 2, false, false>), grid, dim3(256), 0, st, g.p[0]); break; \
-      case 5: hipLaunchKernelGGL((gemm_kernel<T, 32, 32, 2, 2, false, true>), grid, dim3(256), 0, st, g.p[0]); break; \
-      case 6: hipLaunchKernelGGL((gemm_kernel<T, 32, 32, 2, 2, true, false>), grid, dim3(256), 0, st, g.p[0]); break; \
-      default: hipLaunchKernelGGL((gemm_kernel<T, 32, 32, 2, 2, true, true>), grid, dim3(256), 0, st, g.p[0]); break; \
-    }
-    if (dtype == STJ_BF16) { STJ_ONE(bf16) } else if (dtype == STJ_F16) { STJ_ONE(f16) } else { STJ_ONE(float) }
-#undef STJ_ONE
+    stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;          // (the recorded dtype: stj_gemm checked it)
+      switch (c) {
+        case 0: hipLaunchKernelGGL((gemm_kernel<T, 64, 64, 2, 2, false, false>), grid, dim3(256), 0, st, g.p[0]); break;
+        case 1: hipLaunchKernelGGL((gemm_kernel<T, 64, 64, 2, 2, false, true>), grid, dim3(256), 0, st, g.p[0]); break;
+        case 2: hipLaunchKernelGGL((gemm_kernel<T, 64, 64, 2, 2, true, false>), grid, dim3(256), 0, st, g.p[0]); break;
+        case 3: hipLaunchKernelGGL((gemm_kernel<T, 64, 64, 2, 2, true, true>), grid, dim3(256), 0, st, g.p[0]); break;
+        case 4: hipLaunchKernelGGL((gemm_kernel<T, 32, 32, 2, 2, false, false>), grid, dim3(256), 0, st, g.p[0]); break;
+        case 5: hipLaunchKernelGGL((gemm_kernel<T, 32, 32, 2, 2, false, true>), grid, dim3(256), 0, st, g.p[0]); break;
+        case 6: hipLaunchKernelGGL((gemm_kernel<T, 32, 32, 2, 2, true, false>), grid, dim3(256), 0, st, g.p[0]); break;
+        default: hipLaunchKernelGGL((gemm_kernel<T, 32, 32, 2, 2, true, true>), grid, dim3(256), 0, st, g.p[0]); break;
+      }
+    });
     return stj_check_launch("stj_gemm(group of 1)");
   }
   for (int i = 0; i < g.n; ++i) g.cfg[i] &= 7;      // deep k-tile bodies are not in the group kernel (measured: its occupancy drops 4 -> 3, 916 -> 908 scenes/s)
   const int total = g.start[g.n];
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(gemm_group_kernel<bf16>, dim3(total), dim3(256), 0, st, g);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(gemm_group_kernel<f16>, dim3(total), dim3(256), 0, st, g);
-  else hipLaunchKernelGGL(gemm_group_kernel<float>, dim3(total), dim3(256), 0, st, g);
+  stj_with_dtype(dtype, [&](auto t) { hipLaunchKernelGGL(gemm_group_kernel<typename decltype(t)::type>, dim3(total), dim3(256), 0, st, g); });
   return stj_check_launch("stj_gemm(group)");
 }
 
@@ -727,7 +723,7 @@ extern "C" int stj_gemm(const void* A, const void* B, void* C, const float* bias
   p.sBias1 = sBias1; p.sBias2 = sBias2; p.sRes1 = sRes1; p.sRes2 = sRes2; p.ldres = ldres;
   p.act = act; p.c_f32 = c_f32; p.accumulate = accumulate; p.splitk = splitk; p.alpha = alpha;
   p.nkb = nkb; p.sAkb = sAkb; p.sBkb = sBkb;
-  const long long es = stj_is16(dtype) ? 2 : 4;
+  const long long es = stj_elem_bytes(dtype);
   auto al = [&](const void* ptr, long long esz, long long s0, long long s1, long long s2) {
     return ((uintptr_t)ptr % 16 == 0) && ((s0 * esz) % 16 == 0) && ((s1 * esz) % 16 == 0) && ((s2 * esz) % 16 == 0);
   };
@@ -737,11 +733,9 @@ extern "C" int stj_gemm(const void* A, const void* B, void* C, const float* bias
   if (nkb > 1) { p.vecA = p.vecA && (sAkb * es) % 16 == 0; p.vecB = p.vecB && (sBkb * es) % 16 == 0; }
   p.vecC = al(C, c_f32 ? 4 : es, ldc, sCb1, sCb2);
   p.vecR = res ? al(res, es, ldres, sRes1, sRes2) : 0;
-  if (dtype == STJ_BF16) return launch_gemm<bf16>(p, ta, tb, dtype, gs, stream);
-  if (dtype == STJ_F16) return launch_gemm<f16>(p, ta, tb, dtype, gs, stream);
-  if (dtype == STJ_F32) return launch_gemm<float>(p, ta, tb, dtype, gs, stream);
-  stj_set_error("stj_gemm: bad dtype %d", dtype);
-  return STJ_EINVAL;
+  int r = STJ_EINVAL;
+  if (!stj_with_dtype(dtype, [&](auto t) { r = launch_gemm<typename decltype(t)::type>(p, ta, tb, dtype, gs, stream); })) stj_set_error("stj_gemm: bad dtype %d", dtype);
+  return r;
 }
 
 // Group launch: stj_gemm calls that are handed a group (their last pointer argument) are RECORDED into it (arguments validated, their
@@ -807,14 +801,13 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* X, float* out, int
 
 extern "C" int stj_colsum(const void* X, float* out, int M, int N, long long ld, int dtype, hipStream_t stream) {
   if (M <= 0 || N <= 0) return STJ_OK;
-  if (!stj_dtype_ok(dtype)) { stj_set_error("stj_colsum: bad dtype %d", dtype); return STJ_EINVAL; }
-  const long long es = stj_is16(dtype) ? 2 : 4;
+  const long long es = stj_elem_bytes(dtype);
   int rpb = (M + 511) / 512;
   if (rpb < 64) rpb = 64;
   const int vec = ((uintptr_t)X % 16 == 0) && ((ld * es) % 16 == 0);
   dim3 grid((M + rpb - 1) / rpb);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(colsum_kernel<bf16>, grid, dim3(256), 0, stream, (const bf16*)X, out, M, N, ld, rpb, vec);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(colsum_kernel<f16>, grid, dim3(256), 0, stream, (const f16*)X, out, M, N, ld, rpb, vec);
-  else hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, stream, (const float*)X, out, M, N, ld, rpb, vec);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, stream, (const T*)X, out, M, N, ld, rpb, vec);
+      })) { stj_set_error("stj_colsum: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_colsum");
 }

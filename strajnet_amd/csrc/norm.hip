@@ -513,7 +513,7 @@ static int ln_chain_launch(const void* dy, const void* x2, const float* gamma2, 
   return stj_check_launch("stj_layernorm_bwd_chain");
 }
 extern "C" int stj_layernorm_bwd_chain_supported(int C, int dtype) {
-  const int vn = dtype == STJ_F32 ? 4 : 8;
+  const int vn = stj_vec_elems(dtype);
   return stj_dtype_ok(dtype) && C > 0 && C % vn == 0 && C / vn <= 64;
 }
 extern "C" int stj_layernorm_bwd_chain(const void* dy, const void* x2, const float* gamma2, const float* mean2, const float* rstd2, const void* x1,
@@ -527,9 +527,9 @@ extern "C" int stj_layernorm_bwd_chain(const void* dy, const void* x2, const flo
       (((uintptr_t)dy | (uintptr_t)x2 | (uintptr_t)x1 | (uintptr_t)dx1 | (uintptr_t)d2) & 15)) {
     stj_set_error("layernorm_bwd_chain: bad arguments (null / unaligned pointer, nparts / part_stride)"); return STJ_EINVAL;
   }
-  if (dtype == STJ_BF16) return ln_chain_launch<bf16>(dy, x2, gamma2, mean2, rstd2, x1, gamma1, mean1, rstd1, d2, dx1, dgamma2, dbeta2, dgamma1, dbeta1, rows, C, nparts2, part_stride2, nparts1, part_stride1, stream);
-  if (dtype == STJ_F16) return ln_chain_launch<f16>(dy, x2, gamma2, mean2, rstd2, x1, gamma1, mean1, rstd1, d2, dx1, dgamma2, dbeta2, dgamma1, dbeta1, rows, C, nparts2, part_stride2, nparts1, part_stride1, stream);
-  return ln_chain_launch<float>(dy, x2, gamma2, mean2, rstd2, x1, gamma1, mean1, rstd1, d2, dx1, dgamma2, dbeta2, dgamma1, dbeta1, rows, C, nparts2, part_stride2, nparts1, part_stride1, stream);
+  int r = STJ_EUNSUPPORTED;      // (stj_layernorm_bwd_chain_supported: a known dtype)
+  stj_with_dtype(dtype, [&](auto t) { r = ln_chain_launch<typename decltype(t)::type>(dy, x2, gamma2, mean2, rstd2, x1, gamma1, mean1, rstd1, d2, dx1, dgamma2, dbeta2, dgamma1, dbeta1, rows, C, nparts2, part_stride2, nparts1, part_stride1, stream); });
+  return r;
 }
 
 // group_rows/ngroups/gstride: parameter groups (ngroups <= 1: one gamma/beta for all rows).
@@ -540,9 +540,9 @@ extern "C" int stj_layernorm_fwd(const void* x, const float* gamma, const float*
   if (gather_res && (C != 4 * C0 || (gather_res & 1))) { stj_set_error("layernorm: bad gather geometry"); return STJ_EINVAL; }
   if (ngroups > 1 && group_rows <= 0) { stj_set_error("layernorm: bad group_rows"); return STJ_EINVAL; }
   LnGroups G; G.group_rows = group_rows > 0 ? group_rows : rows; G.ngroups = ngroups > 1 ? ngroups : 1; G.gstride = gstride; G.S = 1; G.L = G.group_rows; G.nparts = 1; G.pstride = 0;
-  if (dtype == STJ_BF16) return ln_launch<bf16>(true, x, gamma, beta, y, mean, rstd, nullptr, nullptr, nullptr, nullptr, rows, C, eps, gather_res, C0, G, stream);
-  if (dtype == STJ_F16) return ln_launch<f16>(true, x, gamma, beta, y, mean, rstd, nullptr, nullptr, nullptr, nullptr, rows, C, eps, gather_res, C0, G, stream);
-  return ln_launch<float>(true, x, gamma, beta, y, mean, rstd, nullptr, nullptr, nullptr, nullptr, rows, C, eps, gather_res, C0, G, stream);
+  int r = STJ_EINVAL;
+  if (!stj_with_dtype(dtype, [&](auto t) { r = ln_launch<typename decltype(t)::type>(true, x, gamma, beta, y, mean, rstd, nullptr, nullptr, nullptr, nullptr, rows, C, eps, gather_res, C0, G, stream); })) stj_set_error("stj_layernorm_fwd: bad dtype %d", dtype);
+  return r;
 }
 // y = LayerNorm(x) * gamma + beta + res (res [rows, C], same type): LayerNorm followed by a sum with another branch
 // (the stem's vec + maps before all_patch_norm's input, modules.py:589; Cross_AttentionT's output + query, trajNet.py:305-317).
@@ -552,9 +552,9 @@ extern "C" int stj_layernorm_res_fwd(const void* x, const float* gamma, const fl
   if (rows <= 0) return STJ_OK;
   if (ngroups > 1 && group_rows <= 0) { stj_set_error("layernorm: bad group_rows"); return STJ_EINVAL; }
   LnGroups G; G.group_rows = group_rows > 0 ? group_rows : rows; G.ngroups = ngroups > 1 ? ngroups : 1; G.gstride = gstride; G.S = 1; G.L = G.group_rows; G.nparts = 1; G.pstride = 0;
-  if (dtype == STJ_BF16) return ln_launch<bf16>(true, x, gamma, beta, y, mean, rstd, nullptr, nullptr, nullptr, nullptr, rows, C, eps, 0, 0, G, stream, res);
-  if (dtype == STJ_F16) return ln_launch<f16>(true, x, gamma, beta, y, mean, rstd, nullptr, nullptr, nullptr, nullptr, rows, C, eps, 0, 0, G, stream, res);
-  return ln_launch<float>(true, x, gamma, beta, y, mean, rstd, nullptr, nullptr, nullptr, nullptr, rows, C, eps, 0, 0, G, stream, res);
+  int r = STJ_EINVAL;
+  if (!stj_with_dtype(dtype, [&](auto t) { r = ln_launch<typename decltype(t)::type>(true, x, gamma, beta, y, mean, rstd, nullptr, nullptr, nullptr, nullptr, rows, C, eps, 0, 0, G, stream, res); })) stj_set_error("stj_layernorm_res_fwd: bad dtype %d", dtype);
+  return r;
 }
 extern "C" int stj_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
                                  void* dx, float* dgamma, float* dbeta, long long rows, int C, int gather_res, int C0,
@@ -564,7 +564,7 @@ extern "C" int stj_layernorm_bwd(const void* dy, const void* x, const float* gam
   if (nparts < 1 || (nparts > 1 && part_stride < C)) { stj_set_error("layernorm_bwd: bad nparts / part_stride"); return STJ_EINVAL; }
   if (dres && gather_res) { stj_set_error("layernorm_bwd: dres with the PatchMerging gather is not supported"); return STJ_EINVAL; }
   LnGroups G; G.group_rows = group_rows > 0 ? group_rows : rows; G.ngroups = ngroups > 1 ? ngroups : 1; G.gstride = gstride; G.S = 1; G.L = G.group_rows; G.nparts = nparts; G.pstride = part_stride;
-  if (dtype == STJ_BF16) return ln_launch<bf16>(false, x, gamma, nullptr, nullptr, const_cast<float*>(mean), const_cast<float*>(rstd), dy, dx, dgamma, dbeta, rows, C, 0.f, gather_res, C0, G, stream, dres);
-  if (dtype == STJ_F16) return ln_launch<f16>(false, x, gamma, nullptr, nullptr, const_cast<float*>(mean), const_cast<float*>(rstd), dy, dx, dgamma, dbeta, rows, C, 0.f, gather_res, C0, G, stream, dres);
-  return ln_launch<float>(false, x, gamma, nullptr, nullptr, const_cast<float*>(mean), const_cast<float*>(rstd), dy, dx, dgamma, dbeta, rows, C, 0.f, gather_res, C0, G, stream, dres);
+  int r = STJ_EINVAL;
+  if (!stj_with_dtype(dtype, [&](auto t) { r = ln_launch<typename decltype(t)::type>(false, x, gamma, nullptr, nullptr, const_cast<float*>(mean), const_cast<float*>(rstd), dy, dx, dgamma, dbeta, rows, C, 0.f, gather_res, C0, G, stream, dres); })) stj_set_error("stj_layernorm_bwd: bad dtype %d", dtype);
+  return r;
 }

@@ -241,7 +241,7 @@ extern "C" int stj_patch_embed_fwd(const float* src, const void* w, const float*
     return STJ_EUNSUPPORTED;
   }
   pe::Args a{src, w, bias, gamma, beta, add, gamma2, beta2, cols, pre, x2, y, mean, rstd, mean2, rstd2, B, H, W, pix_stride, ch_stride, eps};
-  if (dtype == STJ_BF16) return pe::by_cin<bf16>(a, Cin, stream);
-  if (dtype == STJ_F16) return pe::by_cin<f16>(a, Cin, stream);
-  return pe::by_cin<float>(a, Cin, stream);
+  int r = STJ_EUNSUPPORTED;      // (stj_patch_embed_supported: a known dtype)
+  stj_with_dtype(dtype, [&](auto t) { r = pe::by_cin<typename decltype(t)::type>(a, Cin, stream); });
+  return r;
 }

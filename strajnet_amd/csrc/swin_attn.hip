@@ -321,16 +321,10 @@ extern "C" int stj_win_attn_fwd(const void* qkv, const float* table, void* out, 
   WinGeom g; g.B = B; g.res = res; g.heads = heads; g.shift = shift; g.nparts = 1;
   g.items = (long long)B * (res / WS) * (res / WS) * heads;
   if (g.items <= 0) return STJ_OK;
-  if (dtype == STJ_BF16) {
-    constexpr int W = WinCfg<bf16>::WPB;
-    hipLaunchKernelGGL(win_attn_fwd_kernel<bf16>, dim3((unsigned)((g.items + W - 1) / W)), dim3(64 * W), 0, stream, (const bf16*)qkv, table, (bf16*)out, g);
-  } else if (dtype == STJ_F16) {
-    constexpr int W = WinCfg<f16>::WPB;
-    hipLaunchKernelGGL(win_attn_fwd_kernel<f16>, dim3((unsigned)((g.items + W - 1) / W)), dim3(64 * W), 0, stream, (const f16*)qkv, table, (f16*)out, g);
-  } else {
-    constexpr int W = WinCfg<float>::WPB;
-    hipLaunchKernelGGL(win_attn_fwd_kernel<float>, dim3((unsigned)((g.items + W - 1) / W)), dim3(64 * W), 0, stream, (const float*)qkv, table, (float*)out, g);
-  }
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        constexpr int W = WinCfg<T>::WPB;
+        hipLaunchKernelGGL(win_attn_fwd_kernel<T>, dim3((unsigned)((g.items + W - 1) / W)), dim3(64 * W), 0, stream, (const T*)qkv, table, (T*)out, g);
+      })) { stj_set_error("stj_win_attn_fwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_win_attn_fwd");
 }
 
@@ -341,15 +335,9 @@ extern "C" int stj_win_attn_bwd(const void* qkv, const float* table, const void*
   WinGeom g; g.B = B; g.res = res; g.heads = heads; g.shift = shift; g.nparts = nparts;
   g.items = (long long)B * (res / WS) * (res / WS) * heads;
   if (g.items <= 0) return STJ_OK;
-  if (dtype == STJ_BF16) {
-    constexpr int W = WinCfg<bf16>::WPB_BWD;
-    hipLaunchKernelGGL(win_attn_bwd_kernel<bf16>, dim3((unsigned)((g.items + W - 1) / W)), dim3(64 * W), 0, stream, (const bf16*)qkv, table, (const bf16*)dout, (bf16*)dqkv, dtable, g);
-  } else if (dtype == STJ_F16) {
-    constexpr int W = WinCfg<f16>::WPB_BWD;
-    hipLaunchKernelGGL(win_attn_bwd_kernel<f16>, dim3((unsigned)((g.items + W - 1) / W)), dim3(64 * W), 0, stream, (const f16*)qkv, table, (const f16*)dout, (f16*)dqkv, dtable, g);
-  } else {
-    constexpr int W = WinCfg<float>::WPB_BWD;
-    hipLaunchKernelGGL(win_attn_bwd_kernel<float>, dim3((unsigned)((g.items + W - 1) / W)), dim3(64 * W), 0, stream, (const float*)qkv, table, (const float*)dout, (float*)dqkv, dtable, g);
-  }
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        constexpr int W = WinCfg<T>::WPB_BWD;
+        hipLaunchKernelGGL(win_attn_bwd_kernel<T>, dim3((unsigned)((g.items + W - 1) / W)), dim3(64 * W), 0, stream, (const T*)qkv, table, (const T*)dout, (T*)dqkv, dtable, g);
+      })) { stj_set_error("stj_win_attn_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_win_attn_bwd");
 }

@@ -1012,11 +1012,9 @@ static int mlp_any(bool bwd, int C, int dtype, const MlpArgs& a, hipStream_t st)
   if (a.M <= 0) return STJ_OK;
   if (a.rows_per_sample < 16 || a.rows_per_sample % 16) { stj_set_error("swin_mlp: rows_per_sample must be a positive multiple of 16"); return STJ_EINVAL; }
   if (!(a.p_drop >= 0.f && a.p_drop < 1.f)) { stj_set_error("swin_mlp: need 0 <= p_drop < 1"); return STJ_EINVAL; }
-  if (dtype == STJ_BF16) return mlp_dispatch<bf16>(bwd, C, a, st);
-  if (dtype == STJ_F16) return mlp_dispatch<f16>(bwd, C, a, st);
-  if (dtype == STJ_F32) return mlp_dispatch<float>(bwd, C, a, st);
-  stj_set_error("swin_mlp: bad dtype %d", dtype);
-  return STJ_EINVAL;
+  int rc = STJ_EINVAL;
+  if (!stj_with_dtype(dtype, [&](auto t) { rc = mlp_dispatch<typename decltype(t)::type>(bwd, C, a, st); })) stj_set_error("swin_mlp: bad dtype %d", dtype);
+  return rc;
 }
 
 // bytes of the f32 workspace `ws` of the four stj_swin_* entry points at C = 384 (NULL: the one-workgroup-per-row-block kernels; other
@@ -1440,11 +1438,9 @@ extern "C" int stj_swin_attn_fwd(const void* x, const float* gamma, const float*
   p.x = x; p.gamma = gamma; p.beta = beta; p.wqkv = wqkv; p.bqkv = bqkv; p.table = table; p.wproj = wproj; p.bproj = bproj; p.y = y;
   p.qkv = qkv; p.a = a; p.ln = ln; p.mean = mean; p.rstd = rstd; p.B = B; p.res = res; p.shift = shift; p.eps = eps;
   p.rng = rng_state; p.site = site; p.p_drop = p_drop; p.part = reinterpret_cast<float*>(ws); p.cnt = split_counters(ws, (long long)B * res * res, C);
-  if (dtype == STJ_BF16) return attn_dispatch<bf16>(C, p, stream);
-  if (dtype == STJ_F16) return attn_dispatch<f16>(C, p, stream);
-  if (dtype == STJ_F32) return attn_dispatch<float>(C, p, stream);
-  stj_set_error("swin_attn: bad dtype %d", dtype);
-  return STJ_EINVAL;
+  int rc = STJ_EINVAL;
+  if (!stj_with_dtype(dtype, [&](auto t) { rc = attn_dispatch<typename decltype(t)::type>(C, p, stream); })) stj_set_error("swin_attn: bad dtype %d", dtype);
+  return rc;
 }
 
 // =====================================================================================================================
@@ -1980,11 +1976,12 @@ extern "C" int stj_swin_attn_bwd(const void* x, const void* dy, const void* qkv,
   p.dx = dx; p.dqkv = dqkv; p.dys = dys; p.dtable = dtable; p.tparts = tparts; p.dgamma = dgamma; p.dbeta = dbeta; p.nparts = nparts;
   p.pstride = part_stride; p.B = B; p.res = res; p.shift = shift; p.rng = rng_state; p.site = site; p.p_drop = p_drop;
   p.part = reinterpret_cast<float*>(ws); p.cnt = split_counters(ws, (long long)B * res * res, C);
-#define STJ_AB(TT) (C == 96 ? attnb_launch<TT, 96>(p, stream) : (C == 192 ? attnb_192<TT>(p, stream) : (C == 384 ? attnb_split384<TT>(p, stream) : (stj_set_error("swin_attn_bwd: C must be 96, 192 or 384 (got %d)", C), (int)STJ_EUNSUPPORTED))))
-  if (dtype == STJ_BF16) return STJ_AB(bf16);
-  if (dtype == STJ_F16) return STJ_AB(f16);
-  if (dtype == STJ_F32) return STJ_AB(float);
-#undef STJ_AB
-  stj_set_error("swin_attn_bwd: bad dtype %d", dtype);
-  return STJ_EINVAL;
+  int rc = STJ_EINVAL;
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        if (C == 96) rc = attnb_launch<T, 96>(p, stream);
+        else if (C == 192) rc = attnb_192<T>(p, stream);
+        else if (C == 384) rc = attnb_split384<T>(p, stream);
+        else { stj_set_error("swin_attn_bwd: C must be 96, 192 or 384 (got %d)", C); rc = STJ_EUNSUPPORTED; }
+      })) stj_set_error("swin_attn_bwd: bad dtype %d", dtype);
+  return rc;
 }

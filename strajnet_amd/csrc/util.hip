@@ -2,6 +2,7 @@
 #include "common.h"
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 static thread_local char g_err[512] = "";
@@ -21,6 +22,10 @@ int stj_check_launch(const char* what) {
   return STJ_OK;
 }
 extern "C" const char* stj_last_error(void) { return g_err; }
+bool stj_no_ws() {   // the rule of ops.py: off exactly when the variable is the string "1" (read once per process)
+  static const bool off = [] { const char* e = getenv("STJ_NO_WS"); return e && strcmp(e, "1") == 0; }();
+  return off;
+}
 extern "C" int stj_abi_version(void) { return 1; }
 
 // One 16-byte vector per thread up to 64 M vectors: short-lived workgroups stream faster than a grid-stride loop over a capped grid
@@ -86,20 +91,20 @@ __global__ __launch_bounds__(256) void unary_bwd_kernel(const T* __restrict__ dy
   for (long long i = nv * VN + blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll)
     stf(dx + i, unary_g<OP, FAST>(ldf(dy + i), ldf(s + i), p0));
 }
-#define UNARY_LAUNCH(KERN, TT, ...)                                                                              \
+#define UNARY_LAUNCH(KERN, ...)   /* inside a stj_with_dtype lambda: T is the element type */                    \
   do {                                                                                                           \
-    if (op == U_GELU) hipLaunchKernelGGL((KERN<TT, U_GELU>), dim3(g), dim3(256), 0, stream, __VA_ARGS__);        \
-    else if (op == U_ELU) hipLaunchKernelGGL((KERN<TT, U_ELU>), dim3(g), dim3(256), 0, stream, __VA_ARGS__);     \
-    else hipLaunchKernelGGL((KERN<TT, U_TANHS>), dim3(g), dim3(256), 0, stream, __VA_ARGS__);                    \
+    if (op == U_GELU) hipLaunchKernelGGL((KERN<T, U_GELU>), dim3(g), dim3(256), 0, stream, __VA_ARGS__);         \
+    else if (op == U_ELU) hipLaunchKernelGGL((KERN<T, U_ELU>), dim3(g), dim3(256), 0, stream, __VA_ARGS__);      \
+    else hipLaunchKernelGGL((KERN<T, U_TANHS>), dim3(g), dim3(256), 0, stream, __VA_ARGS__);                     \
   } while (0)
 extern "C" int stj_unary_fwd(const void* x, void* y, long long n, int op, float p0, int dtype, hipStream_t stream) {
   if (n <= 0) return STJ_OK;
   if (op < U_GELU || op > U_TANHS) { stj_set_error("stj_unary_fwd: bad op %d", op); return STJ_EINVAL; }
   if (((uintptr_t)x | (uintptr_t)y) & 15) { stj_set_error("stj_unary_fwd: pointers must be 16-byte aligned"); return STJ_EINVAL; }
   int g = ew_grid(n / 8);
-  if (dtype == STJ_BF16) UNARY_LAUNCH(unary_fwd_kernel, bf16, (const bf16*)x, (bf16*)y, n, p0);
-  else if (dtype == STJ_F16) UNARY_LAUNCH(unary_fwd_kernel, f16, (const f16*)x, (f16*)y, n, p0);
-  else UNARY_LAUNCH(unary_fwd_kernel, float, (const float*)x, (float*)y, n, p0);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        UNARY_LAUNCH(unary_fwd_kernel, (const T*)x, (T*)y, n, p0);
+      })) { stj_set_error("stj_unary_fwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_unary_fwd");
 }
 extern "C" int stj_unary_bwd(const void* dy, const void* saved, void* dx, long long n, int op, float p0, int dtype, hipStream_t stream) {
@@ -107,9 +112,9 @@ extern "C" int stj_unary_bwd(const void* dy, const void* saved, void* dx, long l
   if (op < U_GELU || op > U_TANHS) { stj_set_error("stj_unary_bwd: bad op %d", op); return STJ_EINVAL; }
   if (((uintptr_t)dy | (uintptr_t)saved | (uintptr_t)dx) & 15) { stj_set_error("stj_unary_bwd: pointers must be 16-byte aligned"); return STJ_EINVAL; }
   int g = ew_grid(n / 8);
-  if (dtype == STJ_BF16) UNARY_LAUNCH(unary_bwd_kernel, bf16, (const bf16*)dy, (const bf16*)saved, (bf16*)dx, n, p0);
-  else if (dtype == STJ_F16) UNARY_LAUNCH(unary_bwd_kernel, f16, (const f16*)dy, (const f16*)saved, (f16*)dx, n, p0);
-  else UNARY_LAUNCH(unary_bwd_kernel, float, (const float*)dy, (const float*)saved, (float*)dx, n, p0);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        UNARY_LAUNCH(unary_bwd_kernel, (const T*)dy, (const T*)saved, (T*)dx, n, p0);
+      })) { stj_set_error("stj_unary_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_unary_bwd");
 }
 
@@ -151,9 +156,9 @@ extern "C" int stj_elu_res_bwd(const void* dy, const void* dy2, const void* y, c
   if ((dy2 == nullptr) != (gsum == nullptr)) { stj_set_error("stj_elu_res_bwd: dy2 and gsum go together"); return STJ_EINVAL; }
   if (((uintptr_t)dy | (uintptr_t)dy2 | (uintptr_t)y | (uintptr_t)r | (uintptr_t)dpre | (uintptr_t)gsum) & 15) { stj_set_error("stj_elu_res_bwd: pointers must be 16-byte aligned"); return STJ_EINVAL; }
   const int g = ew_grid(n / 8);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(elu_res_bwd_kernel<bf16>, dim3(g), dim3(256), 0, stream, (const bf16*)dy, (const bf16*)dy2, (const bf16*)y, (const bf16*)r, (bf16*)dpre, (bf16*)gsum, n);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(elu_res_bwd_kernel<f16>, dim3(g), dim3(256), 0, stream, (const f16*)dy, (const f16*)dy2, (const f16*)y, (const f16*)r, (f16*)dpre, (f16*)gsum, n);
-  else hipLaunchKernelGGL(elu_res_bwd_kernel<float>, dim3(g), dim3(256), 0, stream, (const float*)dy, (const float*)dy2, (const float*)y, (const float*)r, (float*)dpre, (float*)gsum, n);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(elu_res_bwd_kernel<T>, dim3(g), dim3(256), 0, stream, (const T*)dy, (const T*)dy2, (const T*)y, (const T*)r, (T*)dpre, (T*)gsum, n);
+      })) { stj_set_error("stj_elu_res_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_elu_res_bwd");
 }
 
@@ -199,11 +204,10 @@ extern "C" int stj_skip_junction_bwd(const void* dy1, const void* dy2, const voi
   if (((uintptr_t)dy1 | (uintptr_t)dy2 | (uintptr_t)y | (uintptr_t)r1 | (uintptr_t)r2 | (uintptr_t)dpre | (uintptr_t)dr1 | (uintptr_t)dr2) & 15) {
     stj_set_error("stj_skip_junction_bwd: pointers must be 16-byte aligned"); return STJ_EINVAL;
   }
-  if (!stj_dtype_ok(dtype)) { stj_set_error("stj_skip_junction_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
   const int g = ew_grid(n / 8);
-#define SJ_GO(TT) hipLaunchKernelGGL(skip_junction_bwd_kernel<TT>, dim3(g), dim3(256), 0, stream, (const TT*)dy1, (const TT*)dy2, (const TT*)y, (const TT*)r1, (const TT*)r2, (TT*)dpre, (TT*)dr1, (TT*)dr2, n)
-  if (dtype == STJ_BF16) SJ_GO(bf16); else if (dtype == STJ_F16) SJ_GO(f16); else SJ_GO(float);
-#undef SJ_GO
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(skip_junction_bwd_kernel<T>, dim3(g), dim3(256), 0, stream, (const T*)dy1, (const T*)dy2, (const T*)y, (const T*)r1, (const T*)r2, (T*)dpre, (T*)dr1, (T*)dr2, n);
+      })) { stj_set_error("stj_skip_junction_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_skip_junction_bwd");
 }
 
@@ -237,17 +241,17 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const T* dy, const T* 
 extern "C" int stj_maxpool_fwd(const void* x, void* y, int* idx, long long outer, int Tn, int C, int dtype, hipStream_t stream) {
   if (outer <= 0) return STJ_OK;
   int g = ew_grid(outer * C);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(maxpool_fwd_kernel<bf16>, dim3(g), dim3(256), 0, stream, (const bf16*)x, (bf16*)y, idx, outer, Tn, C);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(maxpool_fwd_kernel<f16>, dim3(g), dim3(256), 0, stream, (const f16*)x, (f16*)y, idx, outer, Tn, C);
-  else hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(g), dim3(256), 0, stream, (const float*)x, (float*)y, idx, outer, Tn, C);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(maxpool_fwd_kernel<T>, dim3(g), dim3(256), 0, stream, (const T*)x, (T*)y, idx, outer, Tn, C);
+      })) { stj_set_error("stj_maxpool_fwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_maxpool_fwd");
 }
 extern "C" int stj_maxpool_bwd(const void* dy, const void* x, const void* y, void* dx, long long outer, int Tn, int C, int dtype, hipStream_t stream) {
   if (outer <= 0) return STJ_OK;
   int g = ew_grid(outer * C);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(maxpool_bwd_kernel<bf16>, dim3(g), dim3(256), 0, stream, (const bf16*)dy, (const bf16*)x, (const bf16*)y, (bf16*)dx, outer, Tn, C);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(maxpool_bwd_kernel<f16>, dim3(g), dim3(256), 0, stream, (const f16*)dy, (const f16*)x, (const f16*)y, (f16*)dx, outer, Tn, C);
-  else hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(g), dim3(256), 0, stream, (const float*)dy, (const float*)x, (const float*)y, (float*)dx, outer, Tn, C);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(maxpool_bwd_kernel<T>, dim3(g), dim3(256), 0, stream, (const T*)dy, (const T*)x, (const T*)y, (T*)dx, outer, Tn, C);
+      })) { stj_set_error("stj_maxpool_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_maxpool_bwd");
 }
 
@@ -401,49 +405,44 @@ extern "C" int stj_agent_prep(const float* obs, const float* occ, int n_obs, int
   if (rows <= 0) return STJ_OK;
   if (((uintptr_t)obs | (uintptr_t)occ) & 15) { stj_set_error("stj_agent_prep: obs / occ must be 16-byte aligned"); return STJ_EINVAL; }
   const int g = (rows + 255) / 256;
-#define TT_ARGS(TT) obs, occ, n_obs, n_occ, B, Tn, (TT*)x5, (TT*)v3, vt, cmi, (TT*)cmf
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(agent_prep_kernel<bf16>, dim3(g), dim3(256), 0, stream, TT_ARGS(bf16));
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(agent_prep_kernel<f16>, dim3(g), dim3(256), 0, stream, TT_ARGS(f16));
-  else if (dtype == STJ_F32) hipLaunchKernelGGL(agent_prep_kernel<float>, dim3(g), dim3(256), 0, stream, TT_ARGS(float));
-  else { stj_set_error("stj_agent_prep: bad dtype %d", dtype); return STJ_EINVAL; }
-#undef TT_ARGS
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(agent_prep_kernel<T>, dim3(g), dim3(256), 0, stream, obs, occ, n_obs, n_occ, B, Tn, (T*)x5, (T*)v3, vt, cmi, (T*)cmf);
+      })) { stj_set_error("stj_agent_prep: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_agent_prep");
 }
-#define AGENT_EW(NAME, KERN, G, ARGS_BF, ARGS_H, ARGS_F)                                                             \
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(KERN<bf16>, dim3(G), dim3(256), 0, stream, ARGS_BF);                     \
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(KERN<f16>, dim3(G), dim3(256), 0, stream, ARGS_H);                   \
-  else if (dtype == STJ_F32) hipLaunchKernelGGL(KERN<float>, dim3(G), dim3(256), 0, stream, ARGS_F);                 \
-  else { stj_set_error(NAME ": bad dtype %d", dtype); return STJ_EINVAL; }                                           \
-  return stj_check_launch(NAME)
 extern "C" int stj_agent_mix_fwd(const void* enc, const void* embed, const void* cm, void* concat, void* qin, int B, int A, int C, int dtype,
                                  hipStream_t stream) {
   if ((long long)B * A * C <= 0) return STJ_OK;
   const int g = ew_grid((long long)B * A * C);
-#define A_(TT) (const TT*)enc, (const TT*)embed, (const TT*)cm, (TT*)concat, (TT*)qin, B, A, C
-  AGENT_EW("stj_agent_mix_fwd", agent_mix_fwd_kernel, g, A_(bf16), A_(f16), A_(float));
-#undef A_
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(agent_mix_fwd_kernel<T>, dim3(g), dim3(256), 0, stream, (const T*)enc, (const T*)embed, (const T*)cm, (T*)concat, (T*)qin, B, A, C);
+      })) { stj_set_error("stj_agent_mix_fwd: bad dtype %d", dtype); return STJ_EINVAL; }
+  return stj_check_launch("stj_agent_mix_fwd");
 }
 extern "C" int stj_agent_mix_bwd(const void* dconcat, const void* dqin, const void* cm, void* denc, void* dembed, int B, int A, int C, int dtype,
                                  hipStream_t stream) {
   if ((long long)B * A * C <= 0) return STJ_OK;
   const int g = (A * C + 255) / 256;
-#define A_(TT) (const TT*)dconcat, (const TT*)dqin, (const TT*)cm, (TT*)denc, (TT*)dembed, B, A, C
-  AGENT_EW("stj_agent_mix_bwd", agent_mix_bwd_kernel, g, A_(bf16), A_(f16), A_(float));
-#undef A_
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(agent_mix_bwd_kernel<T>, dim3(g), dim3(256), 0, stream, (const T*)dconcat, (const T*)dqin, (const T*)cm, (T*)denc, (T*)dembed, B, A, C);
+      })) { stj_set_error("stj_agent_mix_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
+  return stj_check_launch("stj_agent_mix_bwd");
 }
 extern "C" int stj_agent_sum_fwd(const void* enc, const void* value, const void* embed, void* out, int B, int A, int C, int dtype, hipStream_t stream) {
   if ((long long)B * A * C <= 0) return STJ_OK;
   const int g = ew_grid((long long)B * A * C);
-#define A_(TT) (const TT*)enc, (const TT*)value, (const TT*)embed, (TT*)out, B, A, C
-  AGENT_EW("stj_agent_sum_fwd", agent_sum_fwd_kernel, g, A_(bf16), A_(f16), A_(float));
-#undef A_
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(agent_sum_fwd_kernel<T>, dim3(g), dim3(256), 0, stream, (const T*)enc, (const T*)value, (const T*)embed, (T*)out, B, A, C);
+      })) { stj_set_error("stj_agent_sum_fwd: bad dtype %d", dtype); return STJ_EINVAL; }
+  return stj_check_launch("stj_agent_sum_fwd");
 }
 extern "C" int stj_agent_sum_bwd(const void* dout, void* dembed, int B, int A, int C, int dtype, hipStream_t stream) {
   if ((long long)B * A * C <= 0) return STJ_OK;
   const int g = (A * C + 255) / 256;
-#define A_(TT) (const TT*)dout, (TT*)dembed, B, A, C
-  AGENT_EW("stj_agent_sum_bwd", agent_sum_bwd_kernel, g, A_(bf16), A_(f16), A_(float));
-#undef A_
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(agent_sum_bwd_kernel<T>, dim3(g), dim3(256), 0, stream, (const T*)dout, (T*)dembed, B, A, C);
+      })) { stj_set_error("stj_agent_sum_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
+  return stj_check_launch("stj_agent_sum_bwd");
 }
 
 // ---- tail of TrajNet.call (trajNet.py:171-187): out = enc + value + embed, then obs_norm on the first n0 agents of a scene and occ_norm on
@@ -560,12 +559,9 @@ extern "C" int stj_agent_out_fwd(const void* enc, const void* value, const void*
   if ((long long)B * A <= 0) return STJ_OK;
   if (C != 384 || n0 < 0 || n0 > A) { stj_set_error("stj_agent_out_fwd: C must be 384 and 0 <= n0 <= A (got C = %d, n0 = %d)", C, n0); return STJ_EUNSUPPORTED; }
   const int g = (B * A + 3) / 4;
-#define A_(TT) (const TT*)enc, (const TT*)value, (const TT*)embed, g0, b0, g1, b1, (TT*)out, (TT*)y, mean, rstd, B, A, n0, eps
-  if (dtype == STJ_BF16) hipLaunchKernelGGL((agent_out_fwd_kernel<bf16, 3>), dim3(g), dim3(256), 0, stream, A_(bf16));
-  else if (dtype == STJ_F16) hipLaunchKernelGGL((agent_out_fwd_kernel<f16, 3>), dim3(g), dim3(256), 0, stream, A_(f16));
-  else if (dtype == STJ_F32) hipLaunchKernelGGL((agent_out_fwd_kernel<float, 3>), dim3(g), dim3(256), 0, stream, A_(float));
-  else { stj_set_error("stj_agent_out_fwd: bad dtype %d", dtype); return STJ_EINVAL; }
-#undef A_
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL((agent_out_fwd_kernel<T, 3>), dim3(g), dim3(256), 0, stream, (const T*)enc, (const T*)value, (const T*)embed, g0, b0, g1, b1, (T*)out, (T*)y, mean, rstd, B, A, n0, eps);
+      })) { stj_set_error("stj_agent_out_fwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_agent_out_fwd");
 }
 extern "C" int stj_agent_out_bwd(const void* dy, const void* out, const float* mean, const float* rstd, const float* g0, const float* g1, void* dout,
@@ -574,22 +570,18 @@ extern "C" int stj_agent_out_bwd(const void* dy, const void* out, const float* m
   if ((long long)B * A <= 0) return STJ_OK;
   if (C != 384 || n0 < 0 || n0 > A) { stj_set_error("stj_agent_out_bwd: C must be 384 and 0 <= n0 <= A (got C = %d, n0 = %d)", C, n0); return STJ_EUNSUPPORTED; }
   const int g = (A + 3) / 4;
-#define A_(TT) (const TT*)dy, (const TT*)out, mean, rstd, g0, g1, (TT*)dout, (TT*)dembed, dg0, db0, dg1, db1, B, A, n0
-  if (dtype == STJ_BF16) hipLaunchKernelGGL((agent_out_bwd_kernel<bf16, 3>), dim3(g), dim3(256), 0, stream, A_(bf16));
-  else if (dtype == STJ_F16) hipLaunchKernelGGL((agent_out_bwd_kernel<f16, 3>), dim3(g), dim3(256), 0, stream, A_(f16));
-  else if (dtype == STJ_F32) hipLaunchKernelGGL((agent_out_bwd_kernel<float, 3>), dim3(g), dim3(256), 0, stream, A_(float));
-  else { stj_set_error("stj_agent_out_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
-#undef A_
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL((agent_out_bwd_kernel<T, 3>), dim3(g), dim3(256), 0, stream, (const T*)dy, (const T*)out, mean, rstd, g0, g1, (T*)dout, (T*)dembed, dg0, db0, dg1, db1, B, A, n0);
+      })) { stj_set_error("stj_agent_out_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_agent_out_bwd");
 }
 
 extern "C" int stj_time_collapse(const float* W, void* Wz, long long n, int dtype, hipStream_t stream) {
   if (n <= 0) return STJ_OK;
   const int g = ew_grid(n);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(time_collapse_kernel<bf16>, dim3(g), dim3(256), 0, stream, W, (bf16*)Wz, n);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(time_collapse_kernel<f16>, dim3(g), dim3(256), 0, stream, W, (f16*)Wz, n);
-  else if (dtype == STJ_F32) hipLaunchKernelGGL(time_collapse_kernel<float>, dim3(g), dim3(256), 0, stream, W, (float*)Wz, n);
-  else { stj_set_error("stj_time_collapse: bad dtype %d", dtype); return STJ_EINVAL; }
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(time_collapse_kernel<T>, dim3(g), dim3(256), 0, stream, W, (T*)Wz, n);
+      })) { stj_set_error("stj_time_collapse: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_time_collapse");
 }
 extern "C" int stj_time_fold(const float* dWz, float* dW, long long n, hipStream_t stream) {

@@ -425,13 +425,10 @@ extern "C" int stj_wgrad_group(const stj_wgrad_job* jobs, int njobs, int dtype, 
     if (total[1] == 0) g0 = G;
     if (g0 < 0 || (total[0] > 0 && g0 == 0)) { g0 = total[0] > 0 ? 1 : 0; if (G < g0 + (total[1] > 0 ? 1 : 0)) G = g0 + 1; }
     d.g0 = (int)g0;
-    if (TN == 96) {
-      if (dtype == STJ_BF16) hipLaunchKernelGGL((wsk::wgrad_sk_kernel<bf16, 96>), dim3((unsigned)G), dim3(256), lds96, stream, d);
-      else hipLaunchKernelGGL((wsk::wgrad_sk_kernel<f16, 96>), dim3((unsigned)G), dim3(256), lds96, stream, d);
-    } else {
-      if (dtype == STJ_BF16) hipLaunchKernelGGL((wsk::wgrad_sk_kernel<bf16, 192>), dim3((unsigned)G), dim3(512), lds192, stream, d);
-      else hipLaunchKernelGGL((wsk::wgrad_sk_kernel<f16, 192>), dim3((unsigned)G), dim3(512), lds192, stream, d);
-    }
+    stj_with_dtype16(dtype, [&](auto t) { typedef typename decltype(t)::type T;      // (wsk_supported: a 16-bit type)
+      if (TN == 96) hipLaunchKernelGGL((wsk::wgrad_sk_kernel<T, 96>), dim3((unsigned)G), dim3(256), lds96, stream, d);
+      else hipLaunchKernelGGL((wsk::wgrad_sk_kernel<T, 192>), dim3((unsigned)G), dim3(512), lds192, stream, d);
+    });
     int e = stj_check_launch("stj_wgrad_group");
     if (e) return e;
   }

@@ -953,22 +953,25 @@ template <typename T> static int launch_fwd(const Args& a, hipStream_t st) {
 
 // bytes of one set's packed weight stream (stj_xattn_pack writes Z of them back to back)
 extern "C" long long stj_xattn_pack_workspace_bytes(int dtype) {
-  return stj_is16(dtype) ? (long long)xat::Geo<bf16>::STREAM * 2 : (long long)xat::Geo<float>::STREAM * 4;
+  long long n = 0;      // (0: not a dtype)
+  stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T; n = (long long)xat::Geo<T>::STREAM * sizeof(T); });
+  return n;
 }
 // bytes the caller adds ONCE behind the Z streams: the kernels copy fixed-size pieces and read this far past the last chunk
 extern "C" long long stj_xattn_pack_tail_workspace_bytes(int dtype) {
-  return stj_is16(dtype) ? (long long)xat::Geo<bf16>::BUFE * 2 : (long long)xat::Geo<float>::BUFE * 4;
+  long long n = 0;
+  stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T; n = (long long)xat::Geo<T>::BUFE * sizeof(T); });
+  return n;
 }
 // wq [3,384,42], wo [3,42,128], w1 [128,512], w2 [512,384] of set 0 (f32 masters; set z lies zstride elements further) -> pack
 extern "C" int stj_xattn_pack(const float* wq, const float* wo, const float* w1, const float* w2, long long zstride, int Z, void* pack, int dtype,
                               hipStream_t stream) {
   if (Z <= 0) return STJ_OK;
-  if (!stj_dtype_ok(dtype)) { stj_set_error("xattn_pack: bad dtype %d", dtype); return STJ_EINVAL; }
   if (((uintptr_t)pack) & 15) { stj_set_error("xattn_pack: pack must be 16-byte aligned"); return STJ_EINVAL; }
   const dim3 grid(128, (unsigned)Z);
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(xat::xattn_pack_kernel<bf16>, grid, dim3(256), 0, stream, wq, wo, w1, w2, zstride, (bf16*)pack);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(xat::xattn_pack_kernel<f16>, grid, dim3(256), 0, stream, wq, wo, w1, w2, zstride, (f16*)pack);
-  else hipLaunchKernelGGL(xat::xattn_pack_kernel<float>, grid, dim3(256), 0, stream, wq, wo, w1, w2, zstride, (float*)pack);
+  if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(xat::xattn_pack_kernel<T>, grid, dim3(256), 0, stream, wq, wo, w1, w2, zstride, (T*)pack);
+      })) { stj_set_error("xattn_pack: bad dtype %d", dtype); return STJ_EINVAL; }
   return stj_check_launch("stj_xattn_pack");
 }
 
@@ -990,11 +993,9 @@ extern "C" int stj_xattn_fwd(const void* query, const void* k, const void* v, co
   a.query = query; a.k = k; a.v = v; a.kvalid = kvalid; a.pack = pack; a.bo = bo; a.g1 = g1; a.be1 = be1; a.b1 = b1; a.b2 = b2; a.g2 = g2;
   a.be2 = be2; a.zstride = zstride; a.y = y; a.sq = sq; a.so = so; a.sv1 = sv1; a.su2 = su2; a.Z = Z; a.B = B; a.HW = HW;
   a.rng = rng_state; a.site_a = site_a; a.site_1 = site_1; a.site_2 = site_2; a.p_drop = p_drop;
-  if (dtype == STJ_BF16) return xat::launch_fwd<bf16>(a, stream);
-  if (dtype == STJ_F16) return xat::launch_fwd<f16>(a, stream);
-  if (dtype == STJ_F32) return xat::launch_fwd<float>(a, stream);
-  stj_set_error("xattn: bad dtype %d", dtype);
-  return STJ_EINVAL;
+  int rc = STJ_EINVAL;
+  if (!stj_with_dtype(dtype, [&](auto t) { rc = xat::launch_fwd<typename decltype(t)::type>(a, stream); })) stj_set_error("xattn: bad dtype %d", dtype);
+  return rc;
 }
 
 // floats of the dk / dv partial-sum workspace of stj_xattn_bwd (each of dkp, dvp)
@@ -1023,17 +1024,14 @@ extern "C" int stj_xattn_bwd(const void* dy, const void* query, const void* k, c
   a.dquery = dquery; a.dkp = dkp; a.dvp = dvp; a.hd = hd; a.dpre = dpre; a.du2 = du2; a.n1 = n1; a.dv1 = dv1; a.dq = dq;
   a.dg1 = dg1; a.dbe1 = dbe1; a.dbo = dbo; a.dg2 = dg2; a.dbe2 = dbe2; a.Z = Z; a.B = B; a.HW = HW;
   a.rng = rng_state; a.site_a = site_a; a.site_1 = site_1; a.site_2 = site_2; a.p_drop = p_drop;
-  int rc;
-  if (dtype == STJ_BF16) rc = xat::launch_bwd<bf16>(a, stream);
-  else if (dtype == STJ_F16) rc = xat::launch_bwd<f16>(a, stream);
-  else if (dtype == STJ_F32) rc = xat::launch_bwd<float>(a, stream);
-  else { stj_set_error("xattn: bad dtype %d", dtype); return STJ_EINVAL; }
+  int rc = STJ_EINVAL;
+  if (!stj_with_dtype(dtype, [&](auto t) { rc = xat::launch_bwd<typename decltype(t)::type>(a, stream); })) stj_set_error("xattn: bad dtype %d", dtype);
   if (rc != STJ_OK) return rc;
   const long long zb = (long long)Z * B, n = 2 * zb * xat::NKEY * xat::NH * xat::HS;
   const int grid = (int)((n + 255) / 256 > 2048 ? 2048 : (n + 255) / 256);
   const int tiles = HW / xat::TOK;
-  if (dtype == STJ_BF16) hipLaunchKernelGGL(xat::xattn_dkv_reduce_kernel<bf16>, dim3(grid), dim3(256), 0, stream, dkp, dvp, (bf16*)dk, (bf16*)dv, zb, tiles);
-  else if (dtype == STJ_F16) hipLaunchKernelGGL(xat::xattn_dkv_reduce_kernel<f16>, dim3(grid), dim3(256), 0, stream, dkp, dvp, (f16*)dk, (f16*)dv, zb, tiles);
-  else hipLaunchKernelGGL(xat::xattn_dkv_reduce_kernel<float>, dim3(grid), dim3(256), 0, stream, dkp, dvp, (float*)dk, (float*)dv, zb, tiles);
+  stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
+    hipLaunchKernelGGL(xat::xattn_dkv_reduce_kernel<T>, dim3(grid), dim3(256), 0, stream, dkp, dvp, (T*)dk, (T*)dv, zb, tiles);
+  });
   return stj_check_launch("stj_xattn_dkv_reduce");
 }
