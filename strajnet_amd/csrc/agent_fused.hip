@@ -44,24 +44,6 @@ constexpr long long P_IW1 = P_IWO + (long long)CB * CB;        // [1536][384]   
 constexpr long long P_IW2 = P_IW1 + (long long)FF * CB;        // [384][1536]     FFN2
 constexpr long long P_TOTAL = P_IW2 + (long long)CB * FF;
 
-template <typename T> __device__ __forceinline__ float exp_t(float x) {
-  if constexpr (sizeof(T) == 4) return expf(x); else return __expf(x);
-}
-template <typename T> __device__ __forceinline__ float elu_t(float x) {
-  if constexpr (sizeof(T) == 4) return elu_f(x); else return elu_bf(x);
-}
-template <typename T> __device__ __forceinline__ float rnd(float x) { T t; stf(&t, x); return ldf(&t); }      // value as the storage type holds it
-__device__ __forceinline__ bool keep1(const long long* rng, int site, long long idx, float p) {
-  bool k[4];
-  keep4(rng, site, idx >> 2, p, k);
-  return k[idx & 3];
-}
-__device__ __forceinline__ void keep_scale4(const long long* rng, int site, long long idx, float p, float sc, float (&f)[4]) {   // idx % 4 == 0
-  bool k[4];
-  keep4(rng, site, idx >> 2, p, k);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) f[e] = k[e] ? sc : 0.f;
-}
 template <typename T> __device__ __forceinline__ void st_acc(T* p, const f32x4& v) { const float t[4] = {v[0], v[1], v[2], v[3]}; st4(p, t); }
 
 // ---- the Dense building block --------------------------------------------------------------------------------------------------------
@@ -1198,18 +1180,11 @@ extern "C" int stj_agent_enc_supported(int n_obs, int n_occ, int Tn, int dtype) 
 
 template <typename T, bool BWD> static int enc_launch(const agf::EncArgs& a, hipStream_t stream) {
   using namespace agf;
-  static PerDevice<int> attr_set;
   const size_t lds = BWD ? enc_bwd_lds<T>() : enc_fwd_lds<T>();
-  const void* fn = BWD ? (const void*)agent_enc_bwd_kernel<T> : (const void*)agent_enc_fwd_kernel<T>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)agent_enc_fwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc_fwd_lds<T>()) != hipSuccess ||
-        hipFuncSetAttribute((const void*)agent_enc_bwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)enc_bwd_lds<T>()) != hipSuccess) {
-      stj_set_error("stj_agent_enc: cannot reserve %zu bytes of LDS", lds);
-      return STJ_ELAUNCH;
-    }
-    attr_set = 1;
+  if (!(BWD ? stj_reserve_lds<agent_enc_bwd_kernel<T>>((int)lds) : stj_reserve_lds<agent_enc_fwd_kernel<T>>((int)lds))) {
+    stj_set_error("stj_agent_enc: cannot reserve %zu bytes of LDS", lds);
+    return STJ_ELAUNCH;
   }
-  (void)fn;
   const int nag = a.B * (a.n_obs + a.n_occ);
   const dim3 grid(nag / EG<T>::AG);
   if (BWD) hipLaunchKernelGGL(agent_enc_bwd_kernel<T>, grid, dim3(256), lds, stream, a);
@@ -1261,26 +1236,21 @@ extern "C" int stj_agent_int_supported(int n_obs, int n_occ, int dtype) { return
 
 template <typename T, bool BWD> static int int_launch(const agf::IntArgs& a, hipStream_t stream) {
   using namespace agf;
-  static PerDevice<int> attr_set;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)agent_int_attn_fwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)int_attn_fwd_lds<T>()) != hipSuccess ||
-        hipFuncSetAttribute((const void*)agent_int_ffn_fwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)int_ffn_lds<T>()) != hipSuccess ||
-        hipFuncSetAttribute((const void*)agent_int_ffn_bwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)int_ffn_lds<T>()) != hipSuccess ||
-        hipFuncSetAttribute((const void*)agent_int_attn_bwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)int_attn_bwd_lds<T>()) != hipSuccess) {
-      stj_set_error("stj_agent_int: cannot reserve %zu bytes of LDS", int_attn_bwd_lds<T>());
-      return STJ_ELAUNCH;
-    }
-    attr_set = 1;
+  const size_t attn_lds = BWD ? int_attn_bwd_lds<T>() : int_attn_fwd_lds<T>(), ffn_lds = int_ffn_lds<T>();
+  if (!(BWD ? stj_reserve_lds<agent_int_ffn_bwd_kernel<T>>((int)ffn_lds) && stj_reserve_lds<agent_int_attn_bwd_kernel<T>>((int)attn_lds)
+            : stj_reserve_lds<agent_int_attn_fwd_kernel<T>>((int)attn_lds) && stj_reserve_lds<agent_int_ffn_fwd_kernel<T>>((int)ffn_lds))) {
+    stj_set_error("stj_agent_int: cannot reserve %zu bytes of LDS", attn_lds > ffn_lds ? attn_lds : ffn_lds);
+    return STJ_ELAUNCH;
   }
   const int rows = a.B * NA;
   if (!BWD) {
-    hipLaunchKernelGGL(agent_int_attn_fwd_kernel<T>, dim3(a.B * IH), dim3(512), int_attn_fwd_lds<T>(), stream, a);
-    hipLaunchKernelGGL(agent_int_ffn_fwd_kernel<T>, dim3(a.B * IGeo<T>::NC), dim3(512), int_ffn_lds<T>(), stream, a);
+    hipLaunchKernelGGL(agent_int_attn_fwd_kernel<T>, dim3(a.B * IH), dim3(512), attn_lds, stream, a);
+    hipLaunchKernelGGL(agent_int_ffn_fwd_kernel<T>, dim3(a.B * IGeo<T>::NC), dim3(512), ffn_lds, stream, a);
     hipLaunchKernelGGL(agent_int_out_fwd_kernel<T>, dim3((rows + 3) / 4), dim3(256), 0, stream, a);
   } else {
     hipLaunchKernelGGL(agent_int_out_bwd_kernel<T>, dim3((rows + 15) / 16), dim3(256), 0, stream, a);
-    hipLaunchKernelGGL(agent_int_ffn_bwd_kernel<T>, dim3(a.B * IGeo<T>::NC), dim3(512), int_ffn_lds<T>(), stream, a);
-    hipLaunchKernelGGL(agent_int_attn_bwd_kernel<T>, dim3(a.B * IH), dim3(512), int_attn_bwd_lds<T>(), stream, a);
+    hipLaunchKernelGGL(agent_int_ffn_bwd_kernel<T>, dim3(a.B * IGeo<T>::NC), dim3(512), ffn_lds, stream, a);
+    hipLaunchKernelGGL(agent_int_attn_bwd_kernel<T>, dim3(a.B * IH), dim3(512), attn_lds, stream, a);
   }
   return stj_check_launch(BWD ? "stj_agent_int_bwd" : "stj_agent_int_fwd");
 }

@@ -57,6 +57,7 @@ template <typename T> __device__ __forceinline__ void stf(T* p, float x);
 template <> __device__ __forceinline__ void stf<float>(float* p, float x) { *p = x; }
 template <> __device__ __forceinline__ void stf<bf16>(bf16* p, float x) { p->v = f2bf(x); }
 template <> __device__ __forceinline__ void stf<f16>(f16* p, float x) { p->v = f2h(x); }
+template <typename T> __device__ __forceinline__ float rnd(float x) { T t; stf(&t, x); return ldf(&t); }      // value as the storage type holds it
 
 // ---- vector (16-byte) global access converted to/from float ---------------------------
 template <typename T> struct Vec;   // elements per 16 bytes
@@ -137,6 +138,13 @@ __device__ __forceinline__ float elu_bf(float x) {
 __device__ __forceinline__ float elu_c(float x) {
   const float e = __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(x * 1.4426950408889634f), 0.f, 1.f);
   return fmaxf(x, e - 1.f);
+}
+// by storage type: libm for the f32 parity mode, the v_exp_f32 forms for the 16-bit types
+template <typename T> __device__ __forceinline__ float exp_t(float x) {
+  if constexpr (sizeof(T) == 4) return expf(x); else return __expf(x);
+}
+template <typename T> __device__ __forceinline__ float elu_t(float x) {
+  if constexpr (sizeof(T) == 4) return elu_f(x); else return elu_bf(x);
 }
 __device__ __forceinline__ float apply_act_fast(float x, int act) {
   return act == 2 ? elu_fast(x) : (act == 1 ? x * 0.5f * (1.f + tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x))) : x);
@@ -253,6 +261,24 @@ template <> struct Mma<f16> : Mma16<f16> {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
   }
 };
+// one MFMA operand fragment <-> the lane's LANE_K consecutive k elements as f32
+template <typename T> __device__ __forceinline__ void frag_unpack(const typename Mma<T>::Frag& f, float* v) {
+  if constexpr (sizeof(T) == 4) { v[0] = f[0]; v[1] = f[1]; v[2] = f[2]; v[3] = f[3]; }
+  else {
+    typedef __attribute__((ext_vector_type(4))) uint32_t u4;
+    const u4 w = __builtin_bit_cast(u4, f);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) unpack2<T>(w[e], v[2 * e], v[2 * e + 1]);
+  }
+}
+template <typename T> __device__ __forceinline__ typename Mma<T>::Frag frag_pack(const float* v) {
+  if constexpr (sizeof(T) == 4) return (f32x4){v[0], v[1], v[2], v[3]};
+  else {
+    typedef __attribute__((ext_vector_type(4))) uint32_t u4;
+    const u4 w = {pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]), pack2<T>(v[4], v[5]), pack2<T>(v[6], v[7])};
+    return __builtin_bit_cast(s16x8, w);
+  }
+}
 
 // sum over the 16 lanes of a DPP row (the lanes of equal lane >> 4); every lane gets the total.  quad_perm xor 1, xor 2, then
 // row_half_mirror / row_mirror (the quads / halves already hold equal values)
@@ -349,3 +375,12 @@ template <typename V> struct PerDevice {
   operator V() { return ref(); }
   PerDevice& operator=(V x) { ref() = x; return *this; }
 };
+// Raise `Kernel`'s dynamic-LDS limit on the current device to at least `bytes`. Host state: largest value set so far, per device.
+template <auto Kernel> static inline bool stj_reserve_lds(int bytes) {
+  static PerDevice<int> reserved;
+  int& r = reserved.ref();
+  if (bytes <= r) return true;
+  if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+  r = bytes;
+  return true;
+}

@@ -448,11 +448,7 @@ static bool upconv_dgrad_pf_try(const void* dP, const void* Wd, void* dX, const 
   if (stj_no_ws() || Hi % TILE_H || Wi % TILE_W || Cin % 64 || Cout % KC || Cin <= 128) return false;
   constexpr int FN = 4, BN = FN * 16, LDK = KC + 8;
   const size_t lds = (size_t)((2 * TILE_H + 2) * (2 * TILE_W + 2) * LDK + 16 * BN * LDK) * sizeof(T);
-  static PerDevice<bool> attr_set;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)upconv_dgrad_pf_kernel<T, FN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-    attr_set = true;
-  }
+  if (!stj_reserve_lds<upconv_dgrad_pf_kernel<T, FN>>((int)lds)) return false;
   const int ntiles = (Wi / TILE_W) * (Hi / TILE_H) * F, ct = Cin / BN;
   // tile sequences: a multiple of 8 (whole XCD rounds of the work map) with all their workgroups resident at once (one per CU, 32 CUs
   // per XCD -- with 85 sequences x 3 cin tiles five XCDs got 33 workgroups and the kernel took two rounds)
@@ -855,10 +851,12 @@ extern "C" int stj_outconv_fwd(const void* X, const float* W, const float* bias,
   const size_t lds = (size_t)(18 * 18 * (C + 1) + 9 * C * 2) * 4;
   if (lds > 160 * 1024) { stj_set_error("outconv: C=%d too large for LDS", C); return STJ_EUNSUPPORTED; }
   const int grid = F * (Hh / OC_T) * (Ww / OC_T);
+  bool reserved = false;      // lds depends on C: the reservation grows with it
   if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
-        hipFuncSetAttribute((const void*)outconv_fwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(outconv_fwd_kernel<T>, dim3(grid), dim3(256), lds, stream, (const T*)X, W, bias, Y, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride);
+        if ((reserved = stj_reserve_lds<outconv_fwd_kernel<T>>((int)lds)))
+          hipLaunchKernelGGL(outconv_fwd_kernel<T>, dim3(grid), dim3(256), lds, stream, (const T*)X, W, bias, Y, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride);
       })) { stj_set_error("stj_outconv_fwd: bad dtype %d", dtype); return STJ_EINVAL; }
+  if (!reserved) { stj_set_error("stj_outconv_fwd: cannot reserve %d bytes of LDS", (int)lds); return STJ_ELAUNCH; }
   return stj_check_launch("stj_outconv_fwd");
 }
 // Both heads of the model output in one launch: Y [B,H,W,4*Tn] f32, channel 4 t + 2 head + o; X0 / X1 the two 48-channel decoder
@@ -926,10 +924,12 @@ extern "C" int stj_outconv_bwd(const void* X, const float* W, const float* dY, v
   const size_t lds = (size_t)(18 * 18 * (C + 1) + 9 * C * 2 + 18 * 18 * 2) * 4;
   if (lds > 160 * 1024 || 9 * C > 1024) { stj_set_error("outconv: C=%d too large", C); return STJ_EUNSUPPORTED; }
   const int grid = min(1024, F * (Hh / OC_T) * (Ww / OC_T));
+  bool reserved = false;      // as in stj_outconv_fwd
   if (!stj_with_dtype(dtype, [&](auto t) { typedef typename decltype(t)::type T;
-        hipFuncSetAttribute((const void*)outconv_bwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(outconv_bwd_kernel<T>, dim3(grid), dim3(256), lds, stream, (const T*)X, W, dY, (T*)dX, dW, db, F, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride, elu_in);
+        if ((reserved = stj_reserve_lds<outconv_bwd_kernel<T>>((int)lds)))
+          hipLaunchKernelGGL(outconv_bwd_kernel<T>, dim3(grid), dim3(256), lds, stream, (const T*)X, W, dY, (T*)dX, dW, db, F, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride, elu_in);
       })) { stj_set_error("stj_outconv_bwd: bad dtype %d", dtype); return STJ_EINVAL; }
+  if (!reserved) { stj_set_error("stj_outconv_bwd: cannot reserve %d bytes of LDS", (int)lds); return STJ_ELAUNCH; }
   return stj_check_launch("stj_outconv_bwd");
 }
 

@@ -208,11 +208,7 @@ static bool fwd_ps_launch(const void* X, const void* Wf, const float* bias, void
   constexpr int LDK = PS_KC + 16, CT = FN * 16, LDO = CT + 8;
   const size_t lds_h = (size_t)2 * (TH + 2) * PS_HW * LDK * 2, lds_o = (size_t)2 * 8 * 2 * PS_TW * LDO * 2;
   const size_t lds = lds_h > lds_o ? lds_h : lds_o;
-  static PerDevice<bool> attr_set;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)upconv_fwd_ps_kernel<T, FN, MINB, TH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-    attr_set = true;
-  }
+  if (!stj_reserve_lds<upconv_fwd_ps_kernel<T, FN, MINB, TH>>((int)lds)) return false;
   const int tiles = ((Wi + PS_TW - 1) / PS_TW) * ((Hi + TH - 1) / TH) * F;
   hipLaunchKernelGGL((upconv_fwd_ps_kernel<T, FN, MINB, TH>), dim3(tiles, (Cout + CT - 1) / CT), dim3(256), lds, st, (const T*)X, (const T*)Wf, bias,
                      (T*)Y, (const T*)R1, (T*)Y2, (const T*)R2, F, Hi, Wi, Cin, Cout);

@@ -383,11 +383,7 @@ template <typename T, int KS, int NF, bool EXACT>
 static bool ws2_launch_t(const void* X, const void* Wf, const float* bias, void* Y, int F, int Hi, int Wi, int Cout, hipStream_t st) {
   constexpr int CIN = KS * 32, LDK = CIN + 16, CT = NF * 16, LDO = CT + 8;
   const size_t lds = (size_t)(2 * WS_HH * WS_HW * LDK + 2 * 8 * 2 * WS_TW * LDO) * 2;
-  static PerDevice<bool> attr_set;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)upconv_fwd_ws2_kernel<T, KS, NF, EXACT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-    attr_set = true;
-  }
+  if (!stj_reserve_lds<upconv_fwd_ws2_kernel<T, KS, NF, EXACT>>((int)lds)) return false;
   const int ntiles = ((Wi + WS_TW - 1) / WS_TW) * ((Hi + WS_TH - 1) / WS_TH) * F;
   const int ct = (Cout + CT - 1) / CT;
   int nblk = 256 / ct;
@@ -397,11 +393,7 @@ static bool ws2_launch_t(const void* X, const void* Wf, const float* bias, void*
   if constexpr (NF == 2) {
     // three cout groups of 32 (the 128 -> 96 layer): 1-D grid, the groups of a walker on one XCD (XCT = 3); walkers a multiple of 8
     if (ct == 3 && ntiles >= 8) {
-      static PerDevice<bool> attr3;
-      if (!attr3) {
-        if (hipFuncSetAttribute((const void*)upconv_fwd_ws2_kernel<T, KS, NF, EXACT, false, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-        attr3 = true;
-      }
+      if (!stj_reserve_lds<upconv_fwd_ws2_kernel<T, KS, NF, EXACT, false, 3>>((int)lds)) return false;
       int nw = 256 / 3 / 8 * 8;                        // 80 walkers x 3 groups = 240 workgroups
       while (nw > 8 && nw - 8 >= ntiles) nw -= 8;
       hipLaunchKernelGGL((upconv_fwd_ws2_kernel<T, KS, NF, EXACT, false, 3>), dim3(nw * 3), dim3(512), lds, st, (const T*)X, (const T*)Wf, bias, (T*)Y, F, Hi, Wi, Cout,
@@ -418,11 +410,7 @@ template <typename T>
 static bool ws2_head_launch(const void* X, const void* Wf, const float* bias, const float* Wh, void* Z, int F, int Hi, int Wi, hipStream_t st) {
   constexpr int KS = 3, NF = 3, CIN = KS * 32, LDK = CIN + 16, CT = NF * 16, LDO = CT + 8;
   const size_t lds = (size_t)(2 * WS_HH * WS_HW * LDK + 2 * 8 * 2 * WS_TW * LDO) * 2;       // (the z stage is smaller than the y stage it replaces)
-  static PerDevice<bool> attr_set;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)upconv_fwd_ws2_kernel<T, KS, NF, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-    attr_set = true;
-  }
+  if (!stj_reserve_lds<upconv_fwd_ws2_kernel<T, KS, NF, true, true>>((int)lds)) return false;
   const int ntiles = (Wi / WS_TW) * (Hi / WS_TH) * F;
   const int nblk = ntiles < 256 ? ntiles : 256;
   hipLaunchKernelGGL((upconv_fwd_ws2_kernel<T, KS, NF, true, true>), dim3(nblk, 1), dim3(512), lds, st, (const T*)X, (const T*)Wf, bias, (T*)Z, F, Hi, Wi, CT, ntiles, 0, Wh);
@@ -793,11 +781,7 @@ static bool wgrad_tr4_launch(const void* X, const void* dP, float* dWeff, float*
                              int tiles, int wg_budget, hipStream_t st) {
   constexpr int CR = NPIX / CW, BO = FO * 16, BI = FI * 16;
   const size_t lds = (size_t)2 * (CR * 2 * CW * (BO + 8) + (CR + 1) * (CW + 2) * ((BI / 16) % 2 ? BI : BI + 16)) * 2;
-  static PerDevice<bool> attr_set;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)upconv_wgrad_tr4_kernel<FO, FI, CW, NPIX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-    attr_set = true;
-  }
+  if (!stj_reserve_lds<upconv_wgrad_tr4_kernel<FO, FI, CW, NPIX>>((int)lds)) return false;
   const long long nchunks = (long long)F * (Hi / CR) * (Wi / CW);
   // Workgroups: HALF the CUs.  Alone the kernel is faster with one workgroup per CU (246 vs 344 us for the 96 -> 48 layer), but the
   // decoder's weight gradients are deferred (ops.py) and run next to the backward of the cross-attentions / FG-MSA / the encoder, chains
@@ -1693,11 +1677,7 @@ template <int KS, int NFI, bool ELU, int COUT>
 static bool dgrad_ws_launch2(const void* dP, const void* Wd, void* dX, const void* Xelu, int F, int Hi, int Wi, int Cin, int Cout, hipStream_t st) {
   constexpr int LDK = KS * 32 + 8, HPIX = (2 * WS_TH + 2) * (2 * WS_TW + 2), CT = NFI * 16, LDR = CT + 4;
   const size_t lds = (size_t)(HPIX * LDK + 64) * 2 + (size_t)2 * 4 * 2 * 16 * LDR * 2;
-  static PerDevice<bool> attr_set;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)upconv_dgrad_ws_kernel<KS, NFI, ELU, COUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-    attr_set = true;
-  }
+  if (!stj_reserve_lds<upconv_dgrad_ws_kernel<KS, NFI, ELU, COUT>>((int)lds)) return false;
   if ((long long)F * 4 * Hi * Wi * Cout * 2 >= (1LL << 31)) return false;      // the halo loader addresses dP through 32-bit (int) byte offsets
   const int ntiles = ((Wi + WS_TW - 1) / WS_TW) * ((Hi + WS_TH - 1) / WS_TH) * F;
   const int ct = (Cin + CT - 1) / CT;
@@ -2102,11 +2082,7 @@ template <bool ELU, bool V3>
 static bool dgrad_ws2_launch(const void* dP, const void* Wd, void* dX, const void* Xelu, int F, int Hi, int Wi, hipStream_t st) {
   constexpr int LDK = 56, HPIX = (2 * WS_TH + 2) * (2 * WS_TW + 2), LDR = 104;
   const size_t lds = (size_t)(HPIX * LDK + 2 * 4 * 2 * 16 * LDR) * 2;
-  static PerDevice<bool> attr_set;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)upconv_dgrad_ws2_kernel<ELU, V3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-    attr_set = true;
-  }
+  if (!stj_reserve_lds<upconv_dgrad_ws2_kernel<ELU, V3>>((int)lds)) return false;
   const int ntiles = ((Wi + WS_TW - 1) / WS_TW) * ((Hi + WS_TH - 1) / WS_TH) * F;
   const int nblk = ntiles < 256 ? ntiles : 256;
   const int dbg = 0;      // (role-ablation mask of the kernel; profiling builds only)

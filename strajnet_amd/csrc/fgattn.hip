@@ -398,17 +398,16 @@ __global__ __launch_bounds__(256) void fgattn_dkv_reduce_kernel(const float* dkp
 template <typename T, int NKF> static int launch(bool bwd, const Args& a, hipStream_t st) {
   const int tt = (2 * a.Hh - 1) * (2 * a.Ww - 1);
   const int lds = bwd ? Lds<T, NKF>::bwd_bytes(tt) : Lds<T, NKF>::fwd_bytes(tt);
-  const void* fn = bwd ? (const void*)fgattn_bwd_kernel<T, NKF> : (const void*)fgattn_fwd_kernel<T, NKF>;
-  static PerDevice<int> reserved[2];           // per (T, NKF) instantiation and direction: the attribute is set once per size, not per launch
   if (lds > 160 * 1024) { stj_set_error("fg_attn: %d bytes of LDS", lds); return STJ_ELAUNCH; }
-  if (lds > reserved[bwd]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      stj_set_error("fg_attn: cannot reserve %d bytes of LDS", lds); return STJ_ELAUNCH;
-    }
-    reserved[bwd] = lds;
+  bool ok;      // lds depends on the map size: the reservation grows with it
+  if (bwd) {
+    if ((ok = stj_reserve_lds<fgattn_bwd_kernel<T, NKF>>(lds)))
+      hipLaunchKernelGGL((fgattn_bwd_kernel<T, NKF>), dim3((unsigned)(a.B * a.G * (16 * NKF / Split<NKF, true, T>::TQ))), dim3(Split<NKF, true, T>::NT), lds, st, a);
+  } else {
+    if ((ok = stj_reserve_lds<fgattn_fwd_kernel<T, NKF>>(lds)))
+      hipLaunchKernelGGL((fgattn_fwd_kernel<T, NKF>), dim3((unsigned)(a.B * a.G * (16 * NKF / Split<NKF, false, T>::TQ))), dim3(Split<NKF, false, T>::NT), lds, st, a);
   }
-  if (bwd) hipLaunchKernelGGL((fgattn_bwd_kernel<T, NKF>), dim3((unsigned)(a.B * a.G * (16 * NKF / Split<NKF, true, T>::TQ))), dim3(Split<NKF, true, T>::NT), lds, st, a);
-  else hipLaunchKernelGGL((fgattn_fwd_kernel<T, NKF>), dim3((unsigned)(a.B * a.G * (16 * NKF / Split<NKF, false, T>::TQ))), dim3(Split<NKF, false, T>::NT), lds, st, a);
+  if (!ok) { stj_set_error("fg_attn: cannot reserve %d bytes of LDS", lds); return STJ_ELAUNCH; }
   return stj_check_launch(bwd ? "stj_fg_attn_bwd" : "stj_fg_attn_fwd");
 }
 template <typename T> static int dispatch(bool bwd, const Args& a, hipStream_t st) {

@@ -34,7 +34,6 @@ template <typename T> struct FG {
   static constexpr long long DIR = (long long)G * NKS * 3 * 64 * LK;   // elements of one direction's pack
 };
 
-template <typename T> __device__ __forceinline__ float rnd(float x) { T t; stf(&t, x); return ldf(&t); }      // value as the storage type holds it
 
 // ---- weight pack: MFMA A fragments in the order the waves load them -----------------------------------------------------------------
 // element ((((dir * 8 + g) * NKS + s) * 3 + mt) * 64 + lane) * LK + j  =  weight of row m = 16 mt + (lane & 15), k = s KSTEP + (lane >> 4) LK + j
@@ -346,18 +345,14 @@ extern "C" int stj_fgoff_pack(const float* w, void* out, int dtype, hipStream_t 
 
 template <typename T, int W, int R, bool BWD> static int fgoff_launch(const fgo::Args& a, hipStream_t stream) {
   using namespace fgo;
-  static PerDevice<int> attr_set;
   constexpr size_t lds = lds_bytes<T, W, R>(BWD);
-  if (!attr_set) {
-    const void* fn = BWD ? (const void*)fgoff_bwd_kernel<T, W, R> : (const void*)fgoff_fwd_kernel<T, W, R>;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      stj_set_error("stj_fgoff: cannot reserve %zu bytes of LDS", lds);
-      return STJ_ELAUNCH;
-    }
-    attr_set = 1;
+  bool ok;
+  if (BWD) {
+    if ((ok = stj_reserve_lds<fgoff_bwd_kernel<T, W, R>>((int)lds))) hipLaunchKernelGGL((fgoff_bwd_kernel<T, W, R>), dim3(a.B * (a.H / R)), dim3(512), lds, stream, a);
+  } else {
+    if ((ok = stj_reserve_lds<fgoff_fwd_kernel<T, W, R>>((int)lds))) hipLaunchKernelGGL((fgoff_fwd_kernel<T, W, R>), dim3(a.B * (a.H / R)), dim3(512), lds, stream, a);
   }
-  if (BWD) hipLaunchKernelGGL((fgoff_bwd_kernel<T, W, R>), dim3(a.B * (a.H / R)), dim3(512), lds, stream, a);
-  else hipLaunchKernelGGL((fgoff_fwd_kernel<T, W, R>), dim3(a.B * (a.H / R)), dim3(512), lds, stream, a);
+  if (!ok) { stj_set_error("stj_fgoff: cannot reserve %zu bytes of LDS", lds); return STJ_ELAUNCH; }
   return stj_check_launch(BWD ? "stj_fgoff_bwd" : "stj_fgoff_fwd");
 }
 template <bool BWD> static int fgoff_run(const stj_fgoff_args* s, hipStream_t stream) {

@@ -409,7 +409,6 @@ static int ln_launch(bool fwd, const void* x, const float* gamma, const float* b
 // d2 is rounded to the storage type before it is used, exactly as the two separate launches hand it over.  Rows are covered as in
 // ln_bwd2_kernel (LPR lanes x one 16-byte chunk, U rows per lane group in flight); plain [rows, C] tensors, one parameter set per norm.
 // =====================================================================================================
-template <typename T> __device__ __forceinline__ float ln_rnd(float x) { T t; stf(&t, x); return ldf(&t); }
 template <typename T, int LPR>
 __global__ __launch_bounds__(256) void ln_bwd_chain_kernel(const T* __restrict__ dy, const T* __restrict__ x2, const float* __restrict__ gamma2,
                                                            const float* __restrict__ mean2, const float* __restrict__ rstd2,
@@ -457,7 +456,7 @@ __global__ __launch_bounds__(256) void ln_bwd_chain_kernel(const T* __restrict__
       s1 = group_sum<LPR>(s1) * invC; s2 = group_sum<LPR>(s2) * invC;
       float d[VN];
 #pragma unroll
-      for (int e = 0; e < VN; ++e) d[e] = ln_rnd<T>(r2[u] * (dv[u][e] - s1 - xa[u][e] * s2));      // as stored by a launch of its own
+      for (int e = 0; e < VN; ++e) d[e] = rnd<T>(r2[u] * (dv[u][e] - s1 - xa[u][e] * s2));      // as stored by a launch of its own
       if (ok && col && d2out) st16(d2out + row * C + c0, d);
       float t1 = 0.f, t2 = 0.f;
 #pragma unroll

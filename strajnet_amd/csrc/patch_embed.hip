@@ -19,7 +19,6 @@
 
 namespace pe {
 
-template <typename T> __device__ __forceinline__ float rnd(float x) { T t; stf(&t, x); return ldf(&t); }   // value as stored in T
 
 constexpr int TOK = 64;       // tokens per workgroup
 constexpr int CO = 96;        // embed_dim (kernel specialisation)
@@ -192,14 +191,10 @@ __global__ __launch_bounds__(256) void patch_embed_fwd_kernel(Args a) {
 
 template <typename T, int CIN>
 static int launch(const Args& a, hipStream_t stream) {
-  static PerDevice<bool> attr;
   const size_t lds = Geo<T>::lds_bytes(16 * CIN);
-  if (!attr) {
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)patch_embed_fwd_kernel<T, CIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      stj_set_error("stj_patch_embed_fwd: cannot reserve %zu bytes of LDS", lds);
-      return STJ_ELAUNCH;
-    }
-    attr = true;
+  if (!stj_reserve_lds<patch_embed_fwd_kernel<T, CIN>>((int)lds)) {
+    stj_set_error("stj_patch_embed_fwd: cannot reserve %zu bytes of LDS", lds);
+    return STJ_ELAUNCH;
   }
   const long long M = (long long)a.B * (a.H / 4) * (a.W / 4);
   hipLaunchKernelGGL((patch_embed_fwd_kernel<T, CIN>), dim3((unsigned)((M + TOK - 1) / TOK)), dim3(256), lds, stream, a);

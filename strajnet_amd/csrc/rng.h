@@ -21,9 +21,22 @@ __device__ __forceinline__ void keep4(const long long* state, int site, long lon
   k[0] = (float)(r.x >> 8) * s >= p; k[1] = (float)(r.y >> 8) * s >= p;
   k[2] = (float)(r.z >> 8) * s >= p; k[3] = (float)(r.w >> 8) * s >= p;
 }
-
+// the keep decision of draw `idx` alone
+__device__ __forceinline__ bool keep1(const long long* rng, int site, long long idx, float p) {
+  bool k[4];
+  keep4(rng, site, idx >> 2, p, k);
+  return k[idx & 3];
+}
+// the keep decisions of the 4 consecutive draws starting at `idx` (idx % 4 == 0), as scale factors
+__device__ __forceinline__ void keep_scale4(const long long* rng, int site, long long idx, float p, float sc, float (&f)[4]) {
+  bool k[4];
+  keep4(rng, site, idx >> 2, p, k);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) f[e] = k[e] ? sc : 0.f;
+}
 
 // DropPath factor of sample `b` at site `site` (reference modules.py:137-151: x / keep * floor(keep + U)); p = 1 - keep.
+// (keep1's step written out: through keep1 the fused Swin backward kernels come out with another register allocation)
 __device__ __forceinline__ float drop_path_scale(const long long* state, int site, long long b, float p) {
   if (state == nullptr || p <= 0.f) return 1.f;
   bool k[4];

@@ -280,23 +280,6 @@ __device__ __forceinline__ void load_rows(typename Mma<T>::Frag (&xa)[RF][C / Mm
     }
   }
 }
-template <typename T> __device__ __forceinline__ void frag_unpack(const typename Mma<T>::Frag& f, float* v) {
-  if constexpr (sizeof(T) == 4) { v[0] = f[0]; v[1] = f[1]; v[2] = f[2]; v[3] = f[3]; }
-  else {
-    typedef __attribute__((ext_vector_type(4))) uint32_t u4;
-    const u4 w = __builtin_bit_cast(u4, f);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) unpack2<T>(w[e], v[2 * e], v[2 * e + 1]);
-  }
-}
-template <typename T> __device__ __forceinline__ typename Mma<T>::Frag frag_pack(const float* v) {
-  if constexpr (sizeof(T) == 4) return (f32x4){v[0], v[1], v[2], v[3]};
-  else {
-    typedef __attribute__((ext_vector_type(4))) uint32_t u4;
-    const u4 w = {pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]), pack2<T>(v[4], v[5]), pack2<T>(v[6], v[7])};
-    return __builtin_bit_cast(s16x8, w);
-  }
-}
 // in-register LayerNorm of the rows held as B fragments (biased variance, eps inside the sqrt: Keras).  Returns mean / rstd of the
 // lane's row in mu[i], rs[i] (identical in the 4 lanes of a row).
 template <typename T, int C, int RF>
@@ -935,17 +918,16 @@ static int attn_split_for(long long windows) { return windows <= 48 ? 6 : 2; }
 template <typename T, int C, int RFP, int SPLIT = 0, int NW = 4, int HS = 1, int HCX = 0>
 static int mlp_launch(bool bwd, const MlpArgs& a, hipStream_t st) {
   typedef MlpCfg<T, C, RFP, NW, HS, HCX> G;
-  const void* fn = bwd ? (const void*)swin_mlp_bwd_kernel<T, C, RFP, SPLIT, NW, HS, HCX> : (const void*)swin_mlp_fwd_kernel<T, C, RFP, SPLIT, NW, HS, HCX>;
-  static PerDevice<bool> attr[2];
-  if (!attr[bwd]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES) != hipSuccess) {
-      stj_set_error("swin_mlp: cannot reserve %d bytes of LDS", G::LDS_BYTES); return STJ_ELAUNCH;
-    }
-    attr[bwd] = true;
-  }
   dim3 grid((unsigned)((a.M + G::ROWS - 1) / G::ROWS) * (SPLIT ? a.split : 1));
-  if (bwd) hipLaunchKernelGGL((swin_mlp_bwd_kernel<T, C, RFP, SPLIT, NW, HS, HCX>), grid, dim3(G::NT), G::LDS_BYTES, st, a);
-  else hipLaunchKernelGGL((swin_mlp_fwd_kernel<T, C, RFP, SPLIT, NW, HS, HCX>), grid, dim3(G::NT), G::LDS_BYTES, st, a);
+  bool ok;
+  if (bwd) {
+    if ((ok = stj_reserve_lds<swin_mlp_bwd_kernel<T, C, RFP, SPLIT, NW, HS, HCX>>(G::LDS_BYTES)))
+      hipLaunchKernelGGL((swin_mlp_bwd_kernel<T, C, RFP, SPLIT, NW, HS, HCX>), grid, dim3(G::NT), G::LDS_BYTES, st, a);
+  } else {
+    if ((ok = stj_reserve_lds<swin_mlp_fwd_kernel<T, C, RFP, SPLIT, NW, HS, HCX>>(G::LDS_BYTES)))
+      hipLaunchKernelGGL((swin_mlp_fwd_kernel<T, C, RFP, SPLIT, NW, HS, HCX>), grid, dim3(G::NT), G::LDS_BYTES, st, a);
+  }
+  if (!ok) { stj_set_error("swin_mlp: cannot reserve %d bytes of LDS", G::LDS_BYTES); return STJ_ELAUNCH; }
   return stj_check_launch(bwd ? "stj_swin_mlp_bwd" : "stj_swin_mlp_fwd");
 }
 template <typename T>
@@ -1372,12 +1354,8 @@ __global__ __launch_bounds__(256, (C == 96 && sizeof(T) == 2) ? STJ_ATTN_MINB96 
 template <typename T, int C, int SPLIT = 0, int HGP = 0>
 static int attn_launch(const AttnArgs& a, hipStream_t st) {
   typedef AttnCfg<T, C, HGP> G;
-  static PerDevice<bool> attr;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)swin_attn_fwd_kernel<T, C, SPLIT, HGP>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES) != hipSuccess) {
-      stj_set_error("swin_attn: cannot reserve %d bytes of LDS", G::LDS_BYTES); return STJ_ELAUNCH;
-    }
-    attr = true;
+  if (!stj_reserve_lds<swin_attn_fwd_kernel<T, C, SPLIT, HGP>>(G::LDS_BYTES)) {
+    stj_set_error("swin_attn: cannot reserve %d bytes of LDS", G::LDS_BYTES); return STJ_ELAUNCH;
   }
   const int nW = (a.res / 8) * (a.res / 8);
   hipLaunchKernelGGL((swin_attn_fwd_kernel<T, C, SPLIT, HGP>), dim3((unsigned)(a.B * nW * (SPLIT ? a.split : 1))), dim3(256), G::LDS_BYTES, st, a);
@@ -1919,12 +1897,8 @@ __global__ __launch_bounds__(256, STJ_ATTNB_MINB) void swin_attn_bwd_kernel(Attn
 template <typename T, int C, int NSPLIT = 1, int HGP = 0, bool FIX = false>
 static int attnb_launch(const AttnBArgs& a, hipStream_t st) {
   typedef AttnBCfg<T, C, HGP> G;
-  static PerDevice<bool> attr;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)swin_attn_bwd_kernel<T, C, NSPLIT, HGP, FIX>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES) != hipSuccess) {
-      stj_set_error("swin_attn_bwd: cannot reserve %d bytes of LDS", G::LDS_BYTES); return STJ_ELAUNCH;
-    }
-    attr = true;
+  if (!stj_reserve_lds<swin_attn_bwd_kernel<T, C, NSPLIT, HGP, FIX>>(G::LDS_BYTES)) {
+    stj_set_error("swin_attn_bwd: cannot reserve %d bytes of LDS", G::LDS_BYTES); return STJ_ELAUNCH;
   }
   const int nW = (a.res / 8) * (a.res / 8);
   hipLaunchKernelGGL((swin_attn_bwd_kernel<T, C, NSPLIT, HGP, FIX>), dim3((unsigned)(a.B * nW * NSPLIT)), dim3(256), G::LDS_BYTES, st, a);

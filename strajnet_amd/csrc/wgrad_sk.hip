@@ -333,18 +333,7 @@ extern "C" int stj_wgrad_group(const stj_wgrad_job* jobs, int njobs, int dtype, 
   if (!jobs) { stj_set_error("stj_wgrad_group: NULL jobs"); return STJ_EINVAL; }
   for (int i = 0; i < njobs; ++i)
     if (!wsk_supported(jobs[i], dtype)) { stj_set_error("stj_wgrad_group: job %d is not supported (see stj_wgrad_job_supported)", i); return STJ_EUNSUPPORTED; }
-  static PerDevice<int> attr_set;
   constexpr int lds96 = wsk::Geo<96>::NS * wsk::Geo<96>::STAGE, lds192 = wsk::Geo<192>::NS * wsk::Geo<192>::STAGE;
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)wsk::wgrad_sk_kernel<bf16, 96>, hipFuncAttributeMaxDynamicSharedMemorySize, lds96) != hipSuccess ||
-        hipFuncSetAttribute((const void*)wsk::wgrad_sk_kernel<f16, 96>, hipFuncAttributeMaxDynamicSharedMemorySize, lds96) != hipSuccess ||
-        hipFuncSetAttribute((const void*)wsk::wgrad_sk_kernel<bf16, 192>, hipFuncAttributeMaxDynamicSharedMemorySize, lds192) != hipSuccess ||
-        hipFuncSetAttribute((const void*)wsk::wgrad_sk_kernel<f16, 192>, hipFuncAttributeMaxDynamicSharedMemorySize, lds192) != hipSuccess) {
-      stj_set_error("stj_wgrad_group: cannot reserve %d bytes of LDS", lds96 > lds192 ? lds96 : lds192);
-      return STJ_ELAUNCH;
-    }
-    attr_set = 1;
-  }
   static PerDevice<int> ncu;
   if (!ncu) {
     int dev = 0; hipDeviceProp_t pr;
@@ -425,10 +414,17 @@ extern "C" int stj_wgrad_group(const stj_wgrad_job* jobs, int njobs, int dtype, 
     if (total[1] == 0) g0 = G;
     if (g0 < 0 || (total[0] > 0 && g0 == 0)) { g0 = total[0] > 0 ? 1 : 0; if (G < g0 + (total[1] > 0 ? 1 : 0)) G = g0 + 1; }
     d.g0 = (int)g0;
+    bool reserved = false;
     stj_with_dtype16(dtype, [&](auto t) { typedef typename decltype(t)::type T;      // (wsk_supported: a 16-bit type)
-      if (TN == 96) hipLaunchKernelGGL((wsk::wgrad_sk_kernel<T, 96>), dim3((unsigned)G), dim3(256), lds96, stream, d);
-      else hipLaunchKernelGGL((wsk::wgrad_sk_kernel<T, 192>), dim3((unsigned)G), dim3(512), lds192, stream, d);
+      if (TN == 96) {
+        if ((reserved = stj_reserve_lds<wsk::wgrad_sk_kernel<T, 96>>(lds96)))
+          hipLaunchKernelGGL((wsk::wgrad_sk_kernel<T, 96>), dim3((unsigned)G), dim3(256), lds96, stream, d);
+      } else {
+        if ((reserved = stj_reserve_lds<wsk::wgrad_sk_kernel<T, 192>>(lds192)))
+          hipLaunchKernelGGL((wsk::wgrad_sk_kernel<T, 192>), dim3((unsigned)G), dim3(512), lds192, stream, d);
+      }
     });
+    if (!reserved) { stj_set_error("stj_wgrad_group: cannot reserve %d bytes of LDS", TN == 96 ? lds96 : lds192); return STJ_ELAUNCH; }
     int e = stj_check_launch("stj_wgrad_group");
     if (e) return e;
   }

@@ -56,13 +56,6 @@ template <typename T> struct Geo {
   static_assert((QCH * ES) % 16 == 0 && (OCH * ES) % 16 == 0 && (FCH * ES) % 16 == 0 && (O1 * LD1 * ES) % 16 == 0, "16-byte chunks");
 };
 
-template <typename T> __device__ __forceinline__ float elu_t(float x) {
-  if constexpr (sizeof(T) == 4) return elu_f(x); else return elu_bf(x);
-}
-template <typename T> __device__ __forceinline__ float exp_t(float x) {
-  if constexpr (sizeof(T) == 4) return expf(x); else return __expf(x);
-}
-
 // ---- weight-chunk staging: flat 16-byte copy global -> registers (one chunk ahead) -> LDS ---------------------------------------
 template <typename T> struct Stage {
   static constexpr int NR = (Geo<T>::BUF * (int)sizeof(T) / 16 + 255) / 256;
@@ -153,14 +146,6 @@ struct Args {
   void* hd; void* dpre; void* du2; void* n1; void* dv1; void* dq;    // operands of the weight-gradient GEMMs, written once
   float* dg1; float* dbe1; float* dbo; float* dg2; float* dbe2;     // "+=" LayerNorm gamma / beta and projection-bias gradients (set 0; set z at + z * zstride)
 };
-
-// dropout keep decisions of the 4 consecutive draws starting at `idx` (idx % 4 == 0), as scale factors
-__device__ __forceinline__ void keep_scale(const long long* rng, int site, long long idx, float p, float sc, float (&f)[4]) {
-  bool k[4];
-  keep4(rng, site, idx >> 2, p, k);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) f[e] = k[e] ? sc : 0.f;
-}
 
 // D[jd] += A^T-image [k = 64 keys][rows = head column] times the chained key-major fragments st[4]   (O^T = V^T P^T, dq^T = K^T dS^T)
 template <typename T>
@@ -289,7 +274,7 @@ __global__ __launch_bounds__(256, 1) void xattn_fwd_kernel(Args p) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float f[4];
-        keep_scale(p.rng, p.site_a, base + 16 * j, p.p_drop, dsc, f);
+        keep_scale4(p.rng, p.site_a, base + 16 * j, p.p_drop, dsc, f);
 #pragma unroll
         for (int r = 0; r < 4; ++r) st[j][r] *= f[r];
       }
@@ -379,7 +364,7 @@ __global__ __launch_bounds__(256, 1) void xattn_fwd_kernel(Args p) {
 #pragma unroll
     for (int d = 0; d < ND; ++d) {
       float f[4] = {1.f, 1.f, 1.f, 1.f};
-      if (train) keep_scale(p.rng, p.site_1, zrow * F1 + c * G::HC + 16 * d + 4 * g, p.p_drop, dsc, f);
+      if (train) keep_scale4(p.rng, p.site_1, zrow * F1 + c * G::HC + 16 * d + 4 * g, p.p_drop, dsc, f);
 #pragma unroll
       for (int r = 0; r < 4; ++r) a1[d][r] = elu_t<T>(a1[d][r]) * f[r];
     }
@@ -401,7 +386,7 @@ __global__ __launch_bounds__(256, 1) void xattn_fwd_kernel(Args p) {
     const int col = 16 * f + 4 * g;
     const float4 bv = *reinterpret_cast<const float4*>(p.b2 + zo + col);
     float fk[4] = {1.f, 1.f, 1.f, 1.f};
-    if (train) keep_scale(p.rng, p.site_2, zrow * CB + col, p.p_drop, dsc, fk);
+    if (train) keep_scale4(p.rng, p.site_2, zrow * CB + col, p.p_drop, dsc, fk);
     o2[f][0] = (o2[f][0] + bv.x) * fk[0]; o2[f][1] = (o2[f][1] + bv.y) * fk[1];
     o2[f][2] = (o2[f][2] + bv.z) * fk[2]; o2[f][3] = (o2[f][3] + bv.w) * fk[3];
     s += o2[f][0] + o2[f][1] + o2[f][2] + o2[f][3];
@@ -494,23 +479,6 @@ template <typename T> struct BGeo {
   static constexpr int NRED = 3 * O1 + 2 * CB + F1;             // LayerNorm / bias gradient sums + the FFN1 bias copy
   static constexpr int LDS_BYTES = (2 * NKEY * G::LDK + NBUF * G::BUF + 2 * TOK * LDP + 2 * TOK * LDT) * (int)sizeof(T) + NKEY * 4 + NRED * 4;
 };
-template <typename T> __device__ __forceinline__ void unpackB(const typename Mma<T>::Frag& f, float* v) {
-  if constexpr (sizeof(T) == 4) { v[0] = f[0]; v[1] = f[1]; v[2] = f[2]; v[3] = f[3]; }
-  else {
-    typedef __attribute__((ext_vector_type(4))) uint32_t u4;
-    const u4 w = __builtin_bit_cast(u4, f);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) unpack2<T>(w[e], v[2 * e], v[2 * e + 1]);
-  }
-}
-template <typename T> __device__ __forceinline__ typename Mma<T>::Frag packB(const float* v) {
-  if constexpr (sizeof(T) == 4) return (f32x4){v[0], v[1], v[2], v[3]};
-  else {
-    typedef __attribute__((ext_vector_type(4))) uint32_t u4;
-    const u4 w = {pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]), pack2<T>(v[4], v[5]), pack2<T>(v[6], v[7])};
-    return __builtin_bit_cast(s16x8, w);
-  }
-}
 // column of element e of chain fragment s (k-step s) held by lane group g
 template <typename T> __device__ __forceinline__ int chain_col(int s, int g, int e) {
   if constexpr (sizeof(T) == 4) return 16 * s + 4 * g + e;
@@ -576,7 +544,7 @@ __global__ __launch_bounds__(256, 1) void xattn_bwd_kernel(Args p) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       float v[LK];
-      unpackB<T>(ub[ks], v);
+      frag_unpack<T>(ub[ks], v);
 #pragma unroll
       for (int e = 0; e < LK; ++e) s += v[e];
     }
@@ -586,7 +554,7 @@ __global__ __launch_bounds__(256, 1) void xattn_bwd_kernel(Args p) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       float v[LK];
-      unpackB<T>(ub[ks], v);
+      frag_unpack<T>(ub[ks], v);
 #pragma unroll
       for (int e = 0; e < LK; ++e) { const float d = v[e] - mean; q += d * d; }
     }
@@ -596,7 +564,7 @@ __global__ __launch_bounds__(256, 1) void xattn_bwd_kernel(Args p) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       float u[LK], d[LK];
-      unpackB<T>(ub[ks], u); unpackB<T>(db[ks], d);
+      frag_unpack<T>(ub[ks], u); frag_unpack<T>(db[ks], d);
       const float* gm = p.g2 + zo + ks * KSTEP + LK * g;
 #pragma unroll
       for (int e = 0; e < LK; ++e) { const float a = d[e] * gm[e]; s1 += a; s2 += a * (u[e] - mean) * rstd; }
@@ -608,13 +576,13 @@ __global__ __launch_bounds__(256, 1) void xattn_bwd_kernel(Args p) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       float u[LK], d[LK], o[LK];
-      unpackB<T>(ub[ks], u); unpackB<T>(db[ks], d);
+      frag_unpack<T>(ub[ks], u); frag_unpack<T>(db[ks], d);
       const int c0 = ks * KSTEP + LK * g;
       const float* gm = p.g2 + zo + c0;
 #pragma unroll
       for (int q4 = 0; q4 < LK / 4; ++q4) {
         float fk[4] = {1.f, 1.f, 1.f, 1.f};
-        if (train) keep_scale(p.rng, p.site_2, zrow * CB + c0 + 4 * q4, p.p_drop, dsc, fk);
+        if (train) keep_scale4(p.rng, p.site_2, zrow * CB + c0 + 4 * q4, p.p_drop, dsc, fk);
 #pragma unroll
         for (int e4 = 0; e4 < 4; ++e4) {
           const int e = 4 * q4 + e4;
@@ -624,7 +592,7 @@ __global__ __launch_bounds__(256, 1) void xattn_bwd_kernel(Args p) {
           rows_to_lds(d[e], red + 3 * O1 + CB + c0 + e, ln);
         }
       }
-      db[ks] = packB<T>(o);
+      db[ks] = frag_pack<T>(o);
       *reinterpret_cast<typename Mma<T>::Frag*>(du2o + ks * KSTEP) = db[ks];
     }
   }
@@ -639,7 +607,7 @@ __global__ __launch_bounds__(256, 1) void xattn_bwd_kernel(Args p) {
     for (int sI = 0; sI < KS1; ++sI) {
       n1c[sI] = Ch<T>::ldB_row(v1p, sI * KSTEP, lane);
       float v[CL];
-      unpackB<T>(n1c[sI], v);
+      frag_unpack<T>(n1c[sI], v);
 #pragma unroll
       for (int e = 0; e < CL; ++e) s += v[e];
     }
@@ -649,7 +617,7 @@ __global__ __launch_bounds__(256, 1) void xattn_bwd_kernel(Args p) {
 #pragma unroll
     for (int sI = 0; sI < KS1; ++sI) {
       float v[CL];
-      unpackB<T>(n1c[sI], v);
+      frag_unpack<T>(n1c[sI], v);
 #pragma unroll
       for (int e = 0; e < CL; ++e) { const float d = v[e] - mean1; q += d * d; }
     }
@@ -659,10 +627,10 @@ __global__ __launch_bounds__(256, 1) void xattn_bwd_kernel(Args p) {
 #pragma unroll
     for (int sI = 0; sI < KS1; ++sI) {
       float v[CL];
-      unpackB<T>(n1c[sI], v);
+      frag_unpack<T>(n1c[sI], v);
 #pragma unroll
       for (int e = 0; e < CL; ++e) { const int col = chain_col<T>(sI, g, e); v[e] = (v[e] - mean1) * rstd1 * p.g1[zo + col] + p.be1[zo + col]; }
-      n1c[sI] = packB<T>(v);
+      n1c[sI] = frag_pack<T>(v);
 #pragma unroll
       for (int h2 = 0; h2 < ND; ++h2) st4(n1o + chain_col<T>(sI, g, 4 * h2), v + 4 * h2);
     }
@@ -703,7 +671,7 @@ __global__ __launch_bounds__(256, 1) void xattn_bwd_kernel(Args p) {
 #pragma unroll
     for (int d = 0; d < ND; ++d) {
       float fk[4] = {1.f, 1.f, 1.f, 1.f};
-      if (train) keep_scale(p.rng, p.site_1, zrow * F1 + c * G::HC + 16 * d + 4 * g, p.p_drop, dsc, fk);
+      if (train) keep_scale4(p.rng, p.site_1, zrow * F1 + c * G::HC + 16 * d + 4 * g, p.p_drop, dsc, fk);
       float hv[4], gv[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -809,7 +777,7 @@ __global__ __launch_bounds__(256, 1) void xattn_bwd_kernel(Args p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float fk[4] = {1.f, 1.f, 1.f, 1.f};
-      if (train) keep_scale(p.rng, p.site_a, base + 16 * j, p.p_drop, dsc, fk);
+      if (train) keep_scale4(p.rng, p.site_a, base + 16 * j, p.p_drop, dsc, fk);
       float pd[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) { pd[r] = st[j][r] * fk[r]; dP[j][r] *= fk[r]; t += st[j][r] * dP[j][r]; }
@@ -923,13 +891,9 @@ __global__ __launch_bounds__(256) void xattn_dkv_reduce_kernel(const float* dkp,
 }
 
 template <typename T> static int launch_bwd(const Args& a, hipStream_t st) {
-  static PerDevice<bool> attr;
   const int lds = BGeo<T>::LDS_BYTES;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)xattn_bwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      stj_set_error("xattn_bwd: cannot reserve %d bytes of LDS", lds); return STJ_ELAUNCH;
-    }
-    attr = true;
+  if (!stj_reserve_lds<xattn_bwd_kernel<T>>(lds)) {
+    stj_set_error("xattn_bwd: cannot reserve %d bytes of LDS", lds); return STJ_ELAUNCH;
   }
   hipLaunchKernelGGL((xattn_bwd_kernel<T>), dim3((unsigned)(a.Z * a.B * (a.HW / TOK))), dim3(256), lds, st, a);
   return stj_check_launch("stj_xattn_bwd");
@@ -938,13 +902,9 @@ template <typename T> static int launch_bwd(const Args& a, hipStream_t st) {
 template <typename T> static int lds_bytes_fwd() { return (2 * NKEY * Geo<T>::LDK + 2 * Geo<T>::BUFE) * (int)sizeof(T) + NKEY * 4 + F1 * 4; }
 
 template <typename T> static int launch_fwd(const Args& a, hipStream_t st) {
-  static PerDevice<bool> attr;
   const int lds = lds_bytes_fwd<T>();
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)xattn_fwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-      stj_set_error("xattn_fwd: cannot reserve %d bytes of LDS", lds); return STJ_ELAUNCH;
-    }
-    attr = true;
+  if (!stj_reserve_lds<xattn_fwd_kernel<T>>(lds)) {
+    stj_set_error("xattn_fwd: cannot reserve %d bytes of LDS", lds); return STJ_ELAUNCH;
   }
   hipLaunchKernelGGL((xattn_fwd_kernel<T>), dim3((unsigned)(a.Z * a.B * (a.HW / TOK))), dim3(256), lds, st, a);
   return stj_check_launch("stj_xattn_fwd");

@@ -214,7 +214,7 @@ def r64(I, fac):
 # ------------------------------------------------------------------------------------------------------------------------------------------
 def twin(I, fac, rd, saves=None):
     """The block as xattn_fwd_kernel / xattn_bwd_kernel evaluate it, in float64 with rd() applied once wherever the kernels turn an f32
-    accumulator into the next product's operand (from_acc, packB) or store it (st4, stf).  rd = identity gives R64 (checked on the CPU).
+    accumulator into the next product's operand (from_acc, frag_pack) or store it (st4, stf).  rd = identity gives R64 (checked on the CPU).
     Rounding points, forward:
       the packed weights Wq, Wo, W1, W2 (stj_xattn_pack; the f32 vectors bo .. be2 are read as they are);
       q, unscaled, before q k^T (the 42^-1/2 multiplies the f32 logits) and as the save sq;
@@ -222,7 +222,7 @@ def twin(I, fac, rd, saves=None):
       n1 = LN1(v1) before FFN1 (v1 itself stays f32 in the forward; the save sv1 is rounded);
       hd = dropout(elu(.)) before FFN2;  the save su2 (LN2 takes the f32 value);  y.
     Backward (reads the saves sq, sv1, su2 as stored -- `saves`, or this function's own forward when None):
-      du2 (packB: the stored tensor IS the operand of W2 du2);  n1 recomputed from the stored v1 (packB);  hd (store only);
+      du2 (frag_pack: the stored tensor IS the operand of W2 du2);  n1 recomputed from the stored v1 (frag_pack);  hd (store only);
       dpre (from_acc, and the store);  dv1 (from_acc, and the store; dbo sums the f32 value);
       dO before dO v^T (HeadOp::from_acc) and in the dO tile of dv = Pd^T dO;
       Pd and dS in their LDS tiles (dk = dS^T q, dv = Pd^T dO) and dS before dq = dS k (from_acc);

@@ -535,6 +535,43 @@ def test_outconv_pair(dt):
         elem_check(f'outconv dparam{i}', p.grad, r.grad, ra.grad, dt)
 
 
+def test_outconv_generic_lds_grows_with_channels():
+    """Raw stj_outconv_fwd / stj_outconv_bwd in f32 (always the generic kernels, whose dynamic LDS grows with the run-time C) at
+    C = 8, 48, 64, 8 in one process and in this order: forward (324 (C + 1) + 18 C) * 4 bytes = 12 KB, 67 KB, 89 KB, 12 KB, i.e. below the
+    64 KB default limit, over it, larger again, smaller again.  A reservation made once per kernel instead of per size fails the C = 64
+    launch with a status code.  One 16 x 16 tile of one frame; references and bounds as in test_outconv_pair."""
+    from strajnet_amd import _lib, ops
+    L = _lib.lib()
+    dt, H = torch.float32, 16
+    cases = {}
+    for C in (8, 48, 64, 8):
+        if C not in cases:
+            x, w, b = rnd((1, H, H, C), dt, 5), rnd((3, 3, C, 2), dt, 1, 0.1), rnd((2,), dt, 2, 0.1)
+            g = rnd((1, H, H, 2), dt, 7)
+            xr, wr, br = ref_of(x), ref_of(w), ref_of(b)
+            xa, wa, ba = ref_of(x.abs()), ref_of(w.abs()), ref_of(b.abs())
+
+            def cv(t, w_, b_):
+                return F.conv2d(t.permute(0, 3, 1, 2), w_.permute(3, 2, 0, 1), b_, padding=1).permute(0, 2, 3, 1)
+            yr, ya = cv(xr, wr, br), cv(xa, wa, ba)
+            yr.backward(g.double().cpu())
+            ya.backward(g.double().cpu().abs())
+            cases[C] = (x, w, b, g, (yr, xr, wr, br), (ya, xa, wa, ba))
+        x, w, b, g, (yr, xr, wr, br), (ya, xa, wa, ba) = cases[C]
+        y, dx, dw, db = torch.empty_like(g), torch.empty_like(x), torch.zeros_like(w), torch.zeros_like(b)      # dW / db are "+="
+        p = lambda t: ops.vp(t.data_ptr())
+        rc_f = L.stj_outconv_fwd(p(x), p(w), p(b), p(y), 1, H, H, C, 1, H * H * 2, 2, 2, 0, ops._st())
+        assert rc_f == 0, (C, rc_f, L.stj_last_error().decode())
+        rc_b = L.stj_outconv_bwd(p(x), p(w), p(g), p(dx), p(dw), p(db), 1, H, H, C, 1, H * H * 2, 2, 2, 0, ops.vp(0), 0, 0, ops._st())
+        assert rc_b == 0, (C, rc_b, L.stj_last_error().decode())
+        torch.cuda.synchronize()
+        for name, got, ref, bound in (('y', y, yr, ya), ('dx', dx, xr.grad, xa.grad), ('dw', dw, wr.grad, wa.grad), ('db', db, br.grad, ba.grad)):
+            e = rel_err(got, ref)
+            print(f'outconv generic C={C} {name}: rel_err {e:.3e}')
+            assert e < tol(dt), (C, name, e)
+            elem_check(f'outconv generic C={C} {name}', got, ref, bound, dt)
+
+
 @pytest.mark.parametrize('dt', [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize('t_major', [True, False])
 def test_inference_heads_in_upconv_epilogue(dt, t_major):
