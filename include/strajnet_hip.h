@@ -567,6 +567,22 @@ int stj_metrics(const float* pred, const float* gt_obs, const float* gt_occ, con
                 int* hist, float* sums, float* auc, float* out, int B, int H, int W, int pred_is_logits, int use_warp,
                 hipStream_t stream);
 
+/* The validation step (train.py:252-282) behind the model: OGMFlow_loss AND the metrics above from ONE pass over the logits [B,H,W,32]
+ * (f32) and the ground truth [B,8,H,W,{1,1,2,1}], instead of stj_loss_auc_gate + stj_loss_fwd + stj_metrics (three passes).
+ * loss f32[5] = observed_xe, occluded_xe, flow, flow_warp_xe, their sum (as stj_loss_fwd); metrics f32[7] (as stj_metrics with
+ * pred_is_logits); gate f32[8] and auc f32[8*4] ([k][gate's, observed, occluded, flow-warped]) optional (NULL).
+ * flags: bits 0-2 as stj_loss_fwd (flow-warp term on, use_focal_loss, use_pred), bit 3 = use_gt (off: every gate 1 and the gate's
+ * AUC 0), bit 4 = the metrics' no_warp (metrics[5], [6] = 0).
+ * workspace: stj_eval_workspace_bytes(B, H, W) bytes, 16-byte aligned, ANY contents on entry (the entry clears what it needs on
+ * `stream`; nothing is read back from an earlier call).
+ * running: optional double[12] = count, the four losses x loss_scale (train.py:275-278 `* REPLICA`), the seven metrics: this
+ * call's values are ADDED and the count incremented (Keras Mean.update_state) by the launch that writes loss and metrics.
+ * No floating-point atomics: two calls on the same inputs give the same bits.  B*H*W <= 0: nothing is launched or written. */
+long long stj_eval_workspace_bytes(int B, int H, int W);
+int stj_eval_fwd(const float* logits, const float* gt_obs, const float* gt_occ, const float* gt_flow, const float* origin,
+                 void* workspace, float* loss, float* metrics, float* gate, float* auc, double* running, int B, int H, int W,
+                 float ogm_w, float occ_w, float flow_origin_w, float replica, float loss_scale, int flags, hipStream_t stream);
+
 /* Training-time randomness.  Keras Dropout / tfa-MHA attention dropout (trajNet.py:33,71,75,77,195,209,211) and DropPath
  * (modules.py:137-151) share one rule: y = [res +] keep(draw) * x / (1 - p), keep = U[0,1) >= p, draw(i) = i / inner
  * (inner = 1: per element; inner = elements per sample: DropPath with p = drop_prob).  U comes from Philox-4x32-10 keyed by

@@ -14,89 +14,11 @@
 //   use_pred (loss.py:253-268)     : q = clip(sig(pred_obs)+sig(pred_occ),0,1) * warp, and only the per-sample-mean BCE
 //                                    survives (loss.py:265 overwrites xe_sum); gradients reach obs, occ and flow logits.
 // Channel slicing of the logits follows train.py:105-123: 4k+0 obs, 4k+1 occ, 4k+2..3 flow (dx,dy).
-#include "common.h"
+#include "loss_pixel.h"      // the per-pixel terms, the warp sample, the AUC bucket and interpolation (shared with csrc/eval.hip)
 
-#define NWP 8
 #define LOSS_PARTS 32
 // per-waypoint accumulator slots
 enum { S_OBS = 0, S_OCC = 1, S_L1 = 2, S_EX = 3, S_WARP = 4, S_N = 5 };
-
-__device__ __forceinline__ float xe_logits(float z, float x) {   // tf.nn.sigmoid_cross_entropy_with_logits
-  return fmaxf(x, 0.f) - x * z + log1pf(__expf(-fabsf(x)));      // v_exp_f32 (1 ulp on a value in (0, 1]); log1p stays exact for small arguments
-}
-__device__ __forceinline__ float sigmoidf(float x) { return __frcp_rn(1.f + __expf(-x)); }
-// XE + tfa focal term on a logit x with label y; *d = derivative w.r.t. x when d != NULL
-__device__ __forceinline__ float xe_focal_logits(float y, float x, float* d) {
-  const float ce = xe_logits(y, x), p = sigmoidf(x);
-  const float pt = y * p + (1.f - y) * (1.f - p), at = y * 0.25f + (1.f - y) * 0.75f, om = 1.f - pt;
-  if (d) {
-    const float dce = p - y, dpt = (2.f * y - 1.f) * p * (1.f - p);
-    *d = dce + at * (om * om * dce - 2.f * om * dpt * ce);
-  }
-  return ce + at * om * om * ce;
-}
-// Keras backend binary_crossentropy(from_logits=False): clip to [eps, 1-eps], -(y log(q+eps) + (1-y) log(1-q+eps));
-// tf.clip_by_value passes the gradient for eps <= q <= 1-eps (bounds included)
-__device__ __forceinline__ float bce_prob(float y, float q, float* d) {
-  const float eps = 1e-7f, hi = 1.f - 1e-7f;
-  const float qc = fminf(fmaxf(q, eps), hi);
-  if (d) *d = (q >= eps && q <= hi) ? (1.f - y) / (1.f - qc + eps) - y / (qc + eps) : 0.f;
-  return -(y * logf(qc + eps) + (1.f - y) * logf(1.f - qc + eps));
-}
-// tfa focal term on a probability q (pred_prob = q unclipped, ce = bce_prob)
-__device__ __forceinline__ float focal_prob(float y, float q, float* d) {
-  float dce;
-  const float ce = bce_prob(y, q, &dce);
-  const float pt = y * q + (1.f - y) * (1.f - q), at = y * 0.25f + (1.f - y) * 0.75f, om = 1.f - pt;
-  if (d) *d = at * (om * om * dce - 2.f * om * (2.f * y - 1.f) * ce);
-  return at * om * om * ce;
-}
-// the warp-consistency pixel term on the joint probability q with label ta; inv_hw = 1 / (H*W)
-template <bool FOCAL, bool PRED>
-__device__ __forceinline__ float warp_term(float ta, float q, float inv_hw, float* d) {
-  if (PRED) {
-    const float v = bce_prob(ta, q, d);
-    if (d) *d *= inv_hw;
-    return v * inv_hw;
-  }
-  if (FOCAL) {
-    float d0, d1;
-    const float v = focal_prob(ta, q, &d0) + bce_prob(ta, q, &d1) * inv_hw;
-    if (d) *d = d0 + d1 * inv_hw;
-    return v;
-  }
-  if (d) *d = sigmoidf(q) - ta;
-  return xe_logits(ta, q);
-}
-
-// bilinear sample of a single-channel [H][W] image at (x,y) (sample(): pad 1, warp+1); optionally d/dx, d/dy
-__device__ __forceinline__ float warp_sample(const float* img, int H, int W, float x, float y, float* ddx, float* ddy) {
-  Bil c = bil_setup(x + 1.f, y + 1.f, H + 2, W + 2);
-  const float tl = pad_at(img, H, W, 1, c.y0, c.x0), tr = pad_at(img, H, W, 1, c.y0, c.x0 + 1);
-  const float bl = pad_at(img, H, W, 1, c.y0 + 1, c.x0), br = pad_at(img, H, W, 1, c.y0 + 1, c.x0 + 1);
-  const float top = c.ax * (tr - tl) + tl, bot = c.ax * (br - bl) + bl;
-  if (ddx) *ddx = c.gx ? (c.ay * (br - bl) + (1.f - c.ay) * (tr - tl)) : 0.f;
-  if (ddy) *ddy = c.gy ? (bot - top) : 0.f;
-  return c.ay * (bot - top) + top;
-}
-
-// Keras AUC bucket of a prediction: the number of thresholds strictly below it, thresholds t0 = -1e-7, t_i = i/99 (i = 1..98),
-// t_99 = 1 + 1e-7 as float32 (tf.keras.metrics.AUC(num_thresholds=100))
-__device__ __forceinline__ int auc_bucket(float pred) {
-  int bk = 0;
-  if (pred > -1e-7f) {
-    bk = 1;
-    int j = (int)(pred * 99.f);
-    j = j < 0 ? 0 : (j > 98 ? 98 : j);
-    // count i in 1..98 with t_i < pred, robust to rounding of pred*99
-    int cnt = j;
-    if (cnt >= 1 && !((float)((double)cnt / 99.0) < pred)) cnt -= 1;
-    else if (cnt < 98 && ((float)((double)(cnt + 1) / 99.0) < pred)) cnt += 1;
-    bk += cnt;
-    if (pred > (float)(1.0 + 1e-7)) bk += 1;
-  }
-  return bk;
-}
 
 // ---- AUC gate ----------------------------------------------------------------------------------------
 // hist [NWP][2][101] (int): bucket = #thresholds strictly below pred; class 1 = label true.
@@ -132,39 +54,13 @@ __global__ __launch_bounds__(256) void auc_hist_kernel(const float* gt_obs, cons
     if (sh[i]) atomicAdd(hist + k * 202 + i, sh[i]);
   if (cnt && threadIdx.x == 0 && sh[202]) atomicAdd(cnt + k, sh[202]);
 }
-// one 128-thread block per waypoint, thread i = threshold i: Keras interpolate_pr_auc from the histogram; gate[k] = auc > 0;
-// auc_out optional.  (v0 ran the whole recurrence in ONE thread per waypoint with 1.6 KB of f64 scratch arrays: 82 us.)
+// one 128-thread block per waypoint, thread i = threshold i: Keras interpolate_pr_auc from the histogram (auc_pr_block); gate[k] = auc > 0;
+// auc_out optional.
 __global__ __launch_bounds__(128) void auc_gate_kernel(const int* hist, float* gate, float* auc_out) {   // gate may be NULL
-  __shared__ int hn[101], hp[101];
-  __shared__ double tp[100], pp[100], part[128];
-  const int k = blockIdx.x, i = threadIdx.x;
-  if (i <= 100) { hn[i] = hist[k * 202 + i]; hp[i] = hist[k * 202 + 101 + i]; }
-  __syncthreads();
-  double totp = 0, totn = 0;
-  for (int j = 0; j <= 100; ++j) { totp += hp[j]; totn += hn[j]; }
-  if (i < 100) {                       // positive at threshold i <=> bucket > i
-    double cp = 0, cn = 0;
-    for (int j = 0; j <= i; ++j) { cp += hp[j]; cn += hn[j]; }
-    tp[i] = totp - cp;
-    pp[i] = tp[i] + (totn - cn);
-  }
-  __syncthreads();
-  double term = 0;
-  if (i < 99) {
-    const double dtp = tp[i] - tp[i + 1], dp = pp[i] - pp[i + 1];
-    const double den = dp > 0 ? dp : 0;
-    const double slope = den != 0 ? dtp / den : 0;
-    const double icpt = tp[i + 1] - slope * pp[i + 1];
-    double ratio = 1.0;
-    if (pp[i] > 0 && pp[i + 1] > 0) ratio = pp[i] / pp[i + 1];
-    const double d2 = totp > 0 ? totp : 0;    // tp + fn = all positives
-    term = d2 != 0 ? slope * (dtp + icpt * log(ratio)) / d2 : 0;
-  }
-  part[i] = term;
-  __syncthreads();
-  if (i == 0) {
-    double auc = 0;
-    for (int j = 0; j < 99; ++j) auc += part[j];          // same summation order as the serial recurrence
+  __shared__ AucScratch s;
+  const int k = blockIdx.x;
+  const double auc = auc_pr_block(hist + k * 202, s);
+  if (threadIdx.x == 0) {
     if (gate) gate[k] = ((1.0 - auc) < 1.0) ? 1.f : 0.f;
     if (auc_out) auc_out[k] = (float)auc;
   }

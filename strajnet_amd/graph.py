@@ -227,3 +227,69 @@ class GraphedForward:
         if self.pipeline_agents and next_batch is not None:
             self.prefetch_agents()
         return self.out
+
+
+class GraphedEvalStep:
+    """hipGraph capture of the validation step (train.py:252-282): the forward pass with training=False, the fused loss + metrics pass
+    (ops.eval_loss_metrics, csrc/eval.hip) and the update of the running means, which that pass's last launch does itself.  The pattern
+    is GraphedForward's (warm-up on the role stream, thread-local capture errors, static inputs), and like it this class opens no stream
+    of its own: the model's side streams are the only ones inside the graph (see GraphedForward on the number of distinct streams).
+    That the step captures at all is the proof that it never waits for the host.
+
+    __call__(batch=None) loads the batch and replays; .logits / .losses / .metrics are static device tensors ([B,H,W,32] f32, the
+    four loss terms, the seven metrics in the order of metrics.FIELDS), .result() the means since the last reset() as a dict
+    (one host sync): the four losses x loss_fn.replica under the names of evaluate.LOSS_KEYS, the metrics under evaluate.METRIC_KEYS."""
+
+    KEYS = ('ogm', 'map_img', 'obs', 'occ', 'flow', 'gt_obs', 'gt_occ', 'gt_flow', 'origin_flow')
+
+    def __init__(self, model, loss_fn, batch, warmup=2, no_warp=False):
+        from .evaluate import eval_loss_metrics
+        self._pass = eval_loss_metrics
+        self.model, self.loss_fn, self.no_warp = model, loss_fn, no_warp
+        self.static = {k: v.clone() for k, v in batch.items() if k in self.KEYS}
+        dev = self.static['ogm'].device
+        self.running = torch.zeros(12, dtype=torch.float64, device=dev)      # count, 4 losses x replica, 7 metrics
+        B, H, W = self.static['gt_obs'].shape[0], self.static['gt_obs'].shape[2], self.static['gt_obs'].shape[3]
+        self._ws = ops.eval_workspace(B, H, W, dev)
+        side = ops.role_stream(torch.cuda.current_device(), 'warmup')
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), torch.no_grad():
+            for _ in range(warmup):
+                self._eager()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        self.running.zero_()                 # the warm-up steps are not part of any mean
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
+            self.logits, self.losses, self.metrics = self._eager()
+
+    def _eager(self):
+        x = self.static
+        out = self.model(x['ogm'], x['map_img'], training=False, obs=x['obs'], occ=x['occ'], mapt=None, flow=x['flow'])
+        d, m = self._pass(self.loss_fn, get_pred_waypoint_logits(out), warpped_gt(x['gt_obs'], x['gt_occ'], x['gt_flow'], x['origin_flow']),
+                          no_warp=self.no_warp, running=self.running, workspace=self._ws)
+        return out, d.packed, m.values
+
+    def load(self, batch):
+        """Copy a new batch into the static input tensors (stream-ordered device copies)."""
+        for k, v in batch.items():
+            if k in self.static:
+                self.static[k].copy_(v, non_blocking=True)
+
+    def __call__(self, batch=None):
+        if batch is not None:
+            self.load(batch)
+        self.graph.replay()
+        return self.losses, self.metrics
+
+    def result(self):
+        """The means over the replays since the last reset() (0.0 each before the first), as {name: float}: one host sync."""
+        from .evaluate import LOSS_KEYS, METRIC_KEYS
+        r = self.running.tolist()
+        n = r[0]
+        keys = LOSS_KEYS + (METRIC_KEYS[:5] if self.no_warp else METRIC_KEYS)
+        return {k: (v / n if n else 0.0) for k, v in zip(keys, r[1:])}
+
+    def reset(self):
+        self.running.zero_()

@@ -2578,3 +2578,47 @@ def auc_gate(gt_obs, gt_occ, gt_flow, origin, return_auc=False):
 def ogm_flow_loss(logits, gt_obs, gt_occ, gt_flow, origin, gate, ogm_w, occ_w, fow, replica, use_warp, coef=None, unit=None):
     """coef + unit: the prepared backward coefficients (loss_coef) and the unit gradient tensor `total` will be differentiated with."""
     return _OgmFlowLoss.apply(logits, gt_obs, gt_occ, gt_flow, origin, gate, ogm_w, occ_w, fow, replica, use_warp, coef, unit)
+
+
+EVAL_USE_GT, EVAL_NO_WARP = 8, 16       # stj_eval_fwd's flag bits beside the loss's three (bit 0 warp term, 1 focal, 2 use_pred)
+
+
+def eval_workspace_bytes(B, H, W):
+    from ._lib import lib
+    return int(lib().stj_eval_workspace_bytes(int(B), int(H), int(W)))
+
+
+def eval_workspace(B, H, W, device):
+    """Scratch of one stj_eval_fwd call (stj_eval_workspace_bytes): any contents, the entry clears what it needs itself."""
+    return torch.empty(eval_workspace_bytes(B, H, W), dtype=torch.uint8, device=device)
+
+
+def eval_loss_metrics(logits, gt_obs, gt_occ, gt_flow, origin, ogm_w, occ_w, fow, replica, flags, running=None, loss_scale=1.0,
+                      workspace=None, with_gate=False):
+    """The validation step's loss and metrics from one pass over the logits [B,H,W,32] and the ground truth (stj_eval_fwd; forward only)
+    -> (loss f32[5] = the four terms and their sum, metrics f32[7] in the order of metrics.FIELDS) [+ gate f32[8], auc f32[8,4] =
+    per waypoint the gate's, observed, occluded, flow-warped AUC].  flags: OGMFlow_loss._flags() | EVAL_USE_GT | EVAL_NO_WARP.
+    running: f64[12] = count, the four losses x loss_scale, the seven metrics; this call's values are added to it on the device."""
+    _req_cuda(logits, gt_obs, gt_occ, gt_flow, origin, running, workspace)
+    logits = logits.detach().contiguous().float()
+    gt_obs, gt_occ, gt_flow, origin = (t.detach().contiguous().float() for t in (gt_obs, gt_occ, gt_flow, origin))
+    B, H, W, C = logits.shape
+    if C != 32 or tuple(gt_obs.shape) != (B, 8, H, W, 1) or tuple(gt_occ.shape) != (B, 8, H, W, 1) or \
+            tuple(gt_flow.shape) != (B, 8, H, W, 2) or tuple(origin.shape) != (B, 8, H, W, 1):
+        raise ValueError('eval_loss_metrics: logits must be [B,H,W,32] and the ground truth [B,8,H,W,{1,1,2,1}]')
+    if running is not None and (running.dtype != torch.float64 or running.numel() != 12 or not running.is_contiguous()):
+        raise ValueError('eval_loss_metrics: running must be a contiguous float64 tensor of 12 elements')
+    dev = logits.device
+    if workspace is None:
+        workspace = eval_workspace(B, H, W, dev)
+    elif workspace.numel() * workspace.element_size() < eval_workspace_bytes(B, H, W):
+        raise ValueError('eval_loss_metrics: the workspace is smaller than stj_eval_workspace_bytes')
+    loss = torch.empty(5, dtype=torch.float32, device=dev)
+    met = torch.empty(7, dtype=torch.float32, device=dev)
+    gate = torch.empty(8, dtype=torch.float32, device=dev) if with_gate else None
+    auc = torch.empty(8, 4, dtype=torch.float32, device=dev) if with_gate else None
+    if B * H * W == 0:           # the entry launches and writes nothing
+        loss.zero_(), met.zero_()
+    call('stj_eval_fwd', _p(logits), _p(gt_obs), _p(gt_occ), _p(gt_flow), _p(origin), _p(workspace), _p(loss), _p(met), _p(gate), _p(auc),
+         _p(running), B, H, W, float(ogm_w), float(occ_w), float(fow), float(replica), float(loss_scale), int(flags), _st())
+    return (loss, met, gate, auc) if with_gate else (loss, met)

@@ -187,6 +187,13 @@ def _loss(fam, tens):
     return f
 
 
+def _eval(a):
+    """stj_eval_fwd(logits, gt_obs, gt_occ, gt_flow, origin, ws, loss, metrics, gate, auc, running, B, H, W, ...): the logits and the five
+    ground-truth floats per (pixel, waypoint), read once."""
+    B, H, W = a[11], a[12], a[13]
+    return f'eval_fwd[B{B} {H}x{W}]', 'eval_fwd', 0.0, 0.0, 4.0 * B * H * W * (32 + 8 * 5)
+
+
 def _patch_embed(a):
     """stj_patch_embed_fwd(src, w, bias, gamma, beta, add, gamma2, beta2, cols, pre, x2, y, mean, rstd, mean2, rstd2, B, H, W, Cin, pix_stride,
     ch_stride, Cout, eps, dtype, stream): reads the f32 raster lines once, writes the tokens (+ cols / pre / x2 in training, + add read)."""
@@ -215,6 +222,7 @@ MODELS = {
     'stj_unary_fwd': _elem('unary_fwd', 2, 5, 2), 'stj_unary_bwd': _elem('unary_bwd', 3, 6, 3),
     'stj_dropout': _elem('dropout', 3, 8, 2),
     'stj_loss_fwd': _loss('loss_fwd', 1), 'stj_loss_bwd': _loss('loss_bwd', 2), 'stj_loss_fwd_bwd': _loss('loss_fwd_bwd', 2),
+    'stj_eval_fwd': _eval,
     'stj_nadam_step': _elem('nadam', 4, 0, 7, f32=True),
 }
 EXTRA_MODELS = {}        # fused kernels register their models here (ops.py)
