@@ -349,10 +349,11 @@ int stj_fg_bias_bwd(const void* off, const float* table, const void* dbias, floa
 /* Fused FG-MSA attention core (FG_MSA.py:138-178; csrc/fgattn.hip): a [B,HW,G*48] = softmax(scale q k^T + sampled bias) v per sample and
  * group, the bias sampled from `table` at the key's offsets as stj_fg_bias_fwd does -- the [B,G,HW,HW] logits / bias / probabilities
  * never reach HBM.  q, k, v [B,HW,G*48], off [B,G,HW,2] (activation dtype), table f32 [2Hh-1,2Ww-1,G]; lse f32 [B,G,HW] (log-sum-exp of
- * each row, the backward's input) or NULL.  Hh = Ww in {8, 16}; dtype STJ_BF16 / STJ_F16 (STJ_F32: STJ_EUNSUPPORTED -- the f32 parity
- * mode runs the layer-by-layer kernels).
- * Backward: dq, dk, dv written (dk / dv through the f32 per-tile partials dkp / dvp, stj_fg_attn_bwd_workspace_bytes() bytes each, and a
- * second launch); dtable f32 "+="; doff f32 [B,G,HW,2] written when Hh = 8 and "+=" (zeroed by the caller) when Hh = 16. */
+ * each row, the backward's input) or NULL.  Hh = Ww in {8, 16} (any other map: STJ_EUNSUPPORTED); STJ_F32, STJ_BF16 and STJ_F16 all run
+ * the fused kernel (f32 with exact-f32 MFMA; its backward takes 16 queries per workgroup on the 16 x 16 map).
+ * Backward: dq, dk, dv written (dk / dv through the f32 per-tile partials dkp / dvp, stj_fg_attn_bwd_workspace_bytes() bytes each, which
+ * need no zeroing, and a second launch); dtable f32 "+="; doff f32 [B,G,HW,2] is WRITTEN when the backward has a single query tile per
+ * (sample, group) -- the 8 x 8 map, every dtype -- and "+=" (zeroed by the caller) otherwise -- the 16 x 16 map: 4 tiles, f32 16. */
 int stj_fg_attn_fwd(const void* q, const void* k, const void* v, const void* off, const float* table, void* a, float* lse, int B, int G,
                     int Hh, int Ww, float scale, int dtype, hipStream_t stream);
 long long stj_fg_attn_bwd_workspace_bytes(int B, int G, int Hh, int Ww);

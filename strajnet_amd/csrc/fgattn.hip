@@ -425,7 +425,8 @@ static int check(int B, int G, int Hh, int Ww, int dtype) {
 }  // namespace fga
 
 // a [B,HW,G*48] = softmax(scale q k^T + sampled bias) v per sample and group; q, k, v [B,HW,G*48], off [B,G,HW,2] (activation dtype),
-// table f32 [2Hh-1, 2Ww-1, G].  lse f32 [B,G,HW] (the rows' log-sum-exp, for the backward) or NULL.  Hh = Ww in {8, 16}; dtype STJ_BF16 / STJ_F16.
+// table f32 [2Hh-1, 2Ww-1, G].  lse f32 [B,G,HW] (the rows' log-sum-exp, for the backward) or NULL.  Hh = Ww in {8, 16}; STJ_F32, STJ_BF16 and
+// STJ_F16 all run the fused kernel.
 extern "C" int stj_fg_attn_fwd(const void* q, const void* k, const void* v, const void* off, const float* table, void* a, float* lse, int B, int G,
                                int Hh, int Ww, float scale, int dtype, hipStream_t stream) {
   const int c = fga::check(B, G, Hh, Ww, dtype);
@@ -442,8 +443,8 @@ extern "C" long long stj_fg_attn_bwd_workspace_bytes(int B, int G, int Hh, int W
   return (long long)B * G * (HW / 16) * HW * fga::D * 4;         // sized for the smallest query tile any dtype uses (f32 on the 16 x 16 map: 16)
 }
 // Backward: a, lse as the forward wrote them, da [B,HW,G*48] -> dq, dk, dv (same shape, written; dk / dv via the f32 per-tile partials
-// dkp / dvp and a second launch), dtable f32 [2Hh-1,2Ww-1,G] "+=", doff f32 [B,G,HW,2]: written when Hh = 8, "+=" (caller zeroes it)
-// when Hh = 16.
+// dkp / dvp and a second launch), dtable f32 [2Hh-1,2Ww-1,G] "+=", doff f32 [B,G,HW,2]: written when the backward has a single query tile
+// (Hh = 8), "+=" (caller zeroes it) otherwise (Hh = 16).
 extern "C" int stj_fg_attn_bwd(const void* q, const void* k, const void* v, const void* off, const float* table, const void* a, const float* lse,
                                const void* da, void* dq, void* dk, void* dv, float* dkp, float* dvp, float* dtable, float* doff, int B, int G,
                                int Hh, int Ww, float scale, int dtype, hipStream_t stream) {
