@@ -600,6 +600,45 @@ int stj_dropout_mask(unsigned char* mask, long long ndraw, float p, const long l
 int stj_nadam_step(float* w, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps,
                    float cg, float cm, float vhat_scale, float gscale, hipStream_t stream);
 
+/* The same Nadam step with its scalar state ON THE DEVICE (train.py:199-230 as one captured graph: by-value coefficients would freeze
+ * at capture time).  Three launches ordered by kernel boundaries alone -- no flag, ticket or spin between workgroups:
+ *   stj_gradnorm_partials   partials[b] = sum of (double)g[i]^2 over workgroup b's grid-stride share, b < STJ_GRADNORM_PARTS.  The grid
+ *                           is fixed, every slot is stored by every call (0.0 where a workgroup has no element) and the fold order is
+ *                           fixed: the same g gives the same bits.  The sum of the slots is non-finite exactly when some g is NaN or
+ *                           +-inf (no term is negative; FLT_MAX^2 is a finite double).
+ *   stj_nadam_prepare       one workgroup, all in double: folds the partials (sumsq), norm = gscale * sqrt(sumsq), decides whether the
+ *                           step is skipped, evaluates the learning-rate schedule at `iterations` (0-based: the first update uses
+ *                           schedule(0)), advances the Keras recurrences with t = iterations + 1
+ *                             mu_t = b1 (1 - 0.5 0.96^(0.004 t)) ; prod_t = m_schedule mu_t ; prod_{t+1} = prod_t mu_{t+1}
+ *                             cg = (1 - mu_t) / (1 - prod_t) ; cm = mu_{t+1} / (1 - prod_{t+1}) ; vhat_scale = 1 / (1 - b2^t)
+ *                             m_schedule <- prod_t ; iterations <- t
+ *                           (b1, b2: the f32 values passed, the ones the element update multiplies by) and writes coef.
+ *                           clipnorm > 0 (tf.clip_by_global_norm): coef.gscale = gscale * clipnorm / max(norm, clipnorm), which IS
+ *                           gscale when norm <= clipnorm.  flags bit 0 (STJ_NADAM_SKIP_NONFINITE): a non-finite sumsq makes
+ *                           coef.apply = 0, skipped += 1 and leaves iterations, m_schedule and state[4] as they were (without the flag the
+ *                           non-finite gradient propagates, as in Keras).  partials == NULL: no norm, no clip, no skip.
+ *                           losses (f32[4]) and running go together (both or neither): running[0] += 1, running[1 + i] +=
+ *                           losses[i] * loss_scale, on EVERY call, skipped or not (train.py:226-229 updates its means unconditionally).
+ *   stj_nadam_apply         stj_nadam_step's element update (csrc/nadam.h) with lr, cg, cm, vhat_scale, gscale read from coef; when
+ *                           coef.apply == 0 no thread reads or writes w, g, m or v.
+ * Device buffers (doubles 8-byte aligned; g, w, m, v and coef 16-byte aligned):
+ *   state   double[8]  [0] iterations (updates applied, 0 at start); [1] m_schedule (product of mu_1..mu_t, 1.0 at start); [2] skipped-
+ *                      step count; [3] last gradient norm (after gscale, before clipping; 0 when not computed); [4] lr of the last
+ *                      applied step; the rest 0
+ *   sched   double[8]  [0] kind (enum stj_optim); STJ_SCHED_CONSTANT {lr}; STJ_SCHED_COSINE_RESTARTS {lr0, first_decay_steps, t_mul,
+ *                      m_mul, alpha} (lr_schedule.py:37-76); STJ_SCHED_CUSTOM {d_model, warmup_steps} (lr_schedule.py:13-17), from [1] on
+ *   coef    float[8]   lr, cg, cm, vhat_scale, gscale, apply (1 or 0), rest 0
+ *   running double[5]  count, then the sums of the four loss terms x loss_scale
+ * n < 0, a null or misaligned buffer, unknown flag bits: STJ_EINVAL, nothing launched.  n == 0: stj_gradnorm_partials still stores
+ * its zeros, stj_nadam_apply launches nothing. */
+enum stj_optim { STJ_GRADNORM_PARTS = 256, STJ_SCHED_CONSTANT = 0, STJ_SCHED_COSINE_RESTARTS = 1, STJ_SCHED_CUSTOM = 2,
+                 STJ_NADAM_SKIP_NONFINITE = 1 };
+int stj_gradnorm_partials(const float* g, long long n, double* partials, hipStream_t stream);
+int stj_nadam_prepare(double* state, const double* sched, const double* partials, float* coef, const float* losses, double* running,
+                      float b1, float b2, float gscale, float clipnorm, float loss_scale, int flags, hipStream_t stream);
+int stj_nadam_apply(float* w, const float* g, float* m, float* v, long long n, const float* coef, float b1, float b2, float eps,
+                    hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,8 @@ The math runs in hand-written HIP kernels (strajnet_amd/csrc -> libstrajnet_hip.
 from .modules import STrajNet            # noqa: F401
 from .loss import (OGMFlow_loss, WaypointGrids, OccupancyFlowTaskConfig,     # noqa: F401
                    get_pred_waypoint_logits, warpped_gt)
-from .optim import Nadam                # noqa: F401
+from .optim import Nadam, DeviceNadam, CosineDecayRestarts, CustomSchedule     # noqa: F401
+from .training import train_step     # noqa: F401
 from .metrics import compute_occupancy_flow_metrics, apply_sigmoid_to_occupancy_logits, OccupancyFlowMetrics     # noqa: F401
 from .evaluate import Mean, OGMFlowMetrics, print_metrics, eval_step     # noqa: F401
 from .submission import (QuantizedWaypoints, ResultDrain, quantize_waypoints, quantize_reference,     # noqa: F401

@@ -1,0 +1,171 @@
+// The Nadam step with its scalar state on the device (reference train.py:199-230 as ONE captured graph): by-value coefficients
+// (stj_nadam_step, csrc/rng.hip) freeze when a hipGraph captures them, so here a kernel advances the step counter, the momentum-cache
+// product and the learning-rate schedule and hands the update its coefficients through a device buffer.  Three launches, ordered by
+// kernel boundaries alone (no flag, ticket or spin between workgroups):
+//   gradnorm_partials_kernel   STJ_GRADNORM_PARTS workgroups, each STORES the double sum of g^2 over its grid-stride share;
+//   nadam_prepare_kernel       one workgroup: folds the partials, decides clip / skip, evaluates the schedule and the Keras
+//                              recurrences in double on one lane, writes coef f32[8], optionally adds the loss terms to running sums;
+//   nadam_apply_kernel         nadam_kernel's element update (csrc/nadam.h) with the coefficients read from coef.
+// The buffers' layouts are in include/strajnet_hip.h.  No floating-point atomics: a fixed grid and a fixed fold order, so the same
+// gradient gives the same norm bits, and with them the same update.
+#include "common.h"
+#include "nadam.h"
+
+#define GRADNORM_THREADS 512
+static_assert(STJ_GRADNORM_PARTS == 256, "nadam_prepare_kernel folds one partial per thread of its 256");
+
+// sum over the workgroup (NW waves), every thread gets it: the wave's xor tree, then the wave totals in index order
+template <int NW>
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = red[0];
+#pragma unroll
+  for (int i = 1; i < NW; ++i) s += red[i];
+  return s;
+}
+// (by the exponent bits: holds whatever the compiler is told about finite math)
+__device__ __forceinline__ bool finite_f64(double x) {
+  return (__double_as_longlong(x) & 0x7ff0000000000000ll) != 0x7ff0000000000000ll;
+}
+
+// HBM-bound: one 16-byte load per four elements; the f32 -> f64 squares are exact and the f64 adds hide under the loads.
+__global__ __launch_bounds__(GRADNORM_THREADS) void gradnorm_partials_kernel(const float* __restrict__ g, long long n,
+                                                                             double* __restrict__ partials) {
+  __shared__ double red[GRADNORM_THREADS / 64];
+  const long long nv = n / 4;
+  double s = 0.0;
+#pragma unroll 4
+  for (long long i = blockIdx.x * (long long)GRADNORM_THREADS + threadIdx.x; i < nv; i += gridDim.x * (long long)GRADNORM_THREADS) {
+    const float4 G = reinterpret_cast<const float4*>(g)[i];
+    s += (double)G.x * (double)G.x + (double)G.y * (double)G.y + (double)G.z * (double)G.z + (double)G.w * (double)G.w;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const double x = g[nv * 4 + threadIdx.x];
+    s += x * x;
+  }
+  s = block_sum_f64<GRADNORM_THREADS / 64>(s, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+// The learning rate at the 0-based step `step`, in double.  sched[0] = kind (enum stj_optim), parameters from sched[1] on.
+//   STJ_SCHED_COSINE_RESTARTS: lr_schedule.py:37-76 (tf.keras CosineDecayRestarts); STJ_SCHED_CUSTOM: lr_schedule.py:13-17
+//   (rsqrt(d_model) min(rsqrt(step), step warmup^-1.5): 0 at step 0, from min(inf, 0)); anything else: the constant sched[1].
+__device__ double schedule_lr(const double* __restrict__ sched, double step) {
+  const int kind = (int)sched[0];
+  if (kind == STJ_SCHED_COSINE_RESTARTS) {
+    const double lr0 = sched[1], first = sched[2], t_mul = sched[3], m_mul = sched[4], alpha = sched[5];
+    double frac = step / first, i_restart;
+    if (t_mul == 1.0) {
+      i_restart = floor(frac);
+      frac -= i_restart;
+    } else {
+      i_restart = floor(log(1.0 - frac * (1.0 - t_mul)) / log(t_mul));
+      const double len = pow(t_mul, i_restart);
+      frac = (frac - (1.0 - len) / (1.0 - t_mul)) / len;
+    }
+    const double cosine = 0.5 * pow(m_mul, i_restart) * (1.0 + cos(3.141592653589793 * frac));
+    return lr0 * ((1.0 - alpha) * cosine + alpha);
+  }
+  if (kind == STJ_SCHED_CUSTOM) return (1.0 / sqrt(sched[1])) * fmin(1.0 / sqrt(step), step * pow(sched[2], -1.5));
+  return sched[1];
+}
+
+struct PrepareCfg { float b1, b2, gscale, clipnorm, loss_scale; int flags; };
+
+__global__ __launch_bounds__(256) void nadam_prepare_kernel(double* __restrict__ state, const double* __restrict__ sched,
+                                                            const double* __restrict__ partials, float* __restrict__ coef,
+                                                            const float* __restrict__ losses, double* __restrict__ running, PrepareCfg c) {
+  __shared__ double red[4];
+  double sumsq = 0.0;
+  if (partials) sumsq = block_sum_f64<4>(partials[threadIdx.x], red);      // (a kernel argument: the whole workgroup takes the branch)
+  if (threadIdx.x != 0) return;
+  if (running) {                                 // Keras Mean.update_state of the four loss terms: every call, skipped or not
+    running[0] += 1.0;
+    for (int i = 0; i < 4; ++i) running[1 + i] += (double)losses[i] * (double)c.loss_scale;
+  }
+  const double norm = partials ? (double)c.gscale * sqrt(sumsq) : 0.0;
+  state[3] = norm;
+  coef[6] = 0.f; coef[7] = 0.f;
+  if (partials && (c.flags & STJ_NADAM_SKIP_NONFINITE) && !finite_f64(sumsq)) {
+    state[2] += 1.0;
+    for (int i = 0; i < 6; ++i) coef[i] = 0.f;   // apply = 0: the update kernel returns before it touches memory
+    return;
+  }
+  double gscale = c.gscale;
+  if (partials && c.clipnorm > 0.f) gscale *= (double)c.clipnorm / fmax(norm, (double)c.clipnorm);      // norm <= clipnorm: * 1.0
+  const double it = state[0], t = it + 1.0, b1 = c.b1, b2 = c.b2;
+  const double lr = schedule_lr(sched, it);
+  const double mu_t = b1 * (1.0 - 0.5 * pow(0.96, 0.004 * t)), mu_n = b1 * (1.0 - 0.5 * pow(0.96, 0.004 * (t + 1.0)));
+  const double prod_t = state[1] * mu_t, prod_n = prod_t * mu_n;
+  state[0] = t;
+  state[1] = prod_t;
+  state[4] = lr;
+  coef[0] = (float)lr;
+  coef[1] = (float)((1.0 - mu_t) / (1.0 - prod_t));
+  coef[2] = (float)(mu_n / (1.0 - prod_n));
+  coef[3] = (float)(1.0 / (1.0 - pow(b2, t)));
+  coef[4] = (float)gscale;
+  coef[5] = 1.f;
+}
+
+__global__ __launch_bounds__(256) void nadam_apply_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
+                                                          float* __restrict__ v, long long n, const float* __restrict__ coef, float b1,
+                                                          float b2, float eps) {
+  if (coef[5] == 0.f) return;                    // a skipped step: nothing of w, g, m, v is read or written
+  const float lr = coef[0], cg = coef[1], cm = coef[2], vhat_scale = coef[3], gscale = coef[4];
+  const long long nv = n / 4;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < nv; i += gridDim.x * 256ll) {
+    float4 W = reinterpret_cast<float4*>(w)[i], G = reinterpret_cast<const float4*>(g)[i];
+    float4 M = reinterpret_cast<float4*>(m)[i], V = reinterpret_cast<float4*>(v)[i];
+    float* wp = &W.x; float* gp = &G.x; float* mp = &M.x; float* vp = &V.x;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) nadam_update(wp[e], gp[e], mp[e], vp[e], lr, b1, b2, eps, cg, cm, vhat_scale, gscale);
+    reinterpret_cast<float4*>(w)[i] = W; reinterpret_cast<float4*>(m)[i] = M; reinterpret_cast<float4*>(v)[i] = V;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const long long i = nv * 4 + threadIdx.x;
+    nadam_update(w[i], g[i], m[i], v[i], lr, b1, b2, eps, cg, cm, vhat_scale, gscale);
+  }
+}
+
+extern "C" int stj_gradnorm_partials(const float* g, long long n, double* partials, hipStream_t stream) {
+  if (n < 0) { stj_set_error("stj_gradnorm_partials: n must not be negative (got %lld)", n); return STJ_EINVAL; }
+  if (!partials || (n > 0 && !g)) { stj_set_error("stj_gradnorm_partials: null pointer"); return STJ_EINVAL; }
+  if (((uintptr_t)g) & 15) { stj_set_error("stj_gradnorm_partials: g must be 16-byte aligned"); return STJ_EINVAL; }
+  if (((uintptr_t)partials) & 7) { stj_set_error("stj_gradnorm_partials: partials must be 8-byte aligned"); return STJ_EINVAL; }
+  hipLaunchKernelGGL(gradnorm_partials_kernel, dim3(STJ_GRADNORM_PARTS), dim3(GRADNORM_THREADS), 0, stream, g, n, partials);
+  return stj_check_launch("stj_gradnorm_partials");
+}
+
+extern "C" int stj_nadam_prepare(double* state, const double* sched, const double* partials, float* coef, const float* losses,
+                                 double* running, float b1, float b2, float gscale, float clipnorm, float loss_scale, int flags,
+                                 hipStream_t stream) {
+  if (!state || !sched || !coef) { stj_set_error("stj_nadam_prepare: state, sched and coef must not be null"); return STJ_EINVAL; }
+  if ((losses == nullptr) != (running == nullptr)) { stj_set_error("stj_nadam_prepare: losses and running go together"); return STJ_EINVAL; }
+  if (((uintptr_t)state | (uintptr_t)sched | (uintptr_t)partials | (uintptr_t)running) & 7) {
+    stj_set_error("stj_nadam_prepare: state, sched, partials and running must be 8-byte aligned"); return STJ_EINVAL;
+  }
+  if (((uintptr_t)coef) & 15) { stj_set_error("stj_nadam_prepare: coef must be 16-byte aligned"); return STJ_EINVAL; }
+  if (((uintptr_t)losses) & 3) { stj_set_error("stj_nadam_prepare: losses must be 4-byte aligned"); return STJ_EINVAL; }
+  if (flags & ~STJ_NADAM_SKIP_NONFINITE) { stj_set_error("stj_nadam_prepare: unknown flag bits %d", flags); return STJ_EINVAL; }
+  PrepareCfg c; c.b1 = b1; c.b2 = b2; c.gscale = gscale; c.clipnorm = clipnorm; c.loss_scale = loss_scale; c.flags = flags;
+  hipLaunchKernelGGL(nadam_prepare_kernel, dim3(1), dim3(256), 0, stream, state, sched, partials, coef, losses, running, c);
+  return stj_check_launch("stj_nadam_prepare");
+}
+
+extern "C" int stj_nadam_apply(float* w, const float* g, float* m, float* v, long long n, const float* coef, float b1, float b2, float eps,
+                               hipStream_t stream) {
+  if (n < 0) { stj_set_error("stj_nadam_apply: n must not be negative (got %lld)", n); return STJ_EINVAL; }
+  if (n == 0) return STJ_OK;
+  if (!w || !g || !m || !v || !coef) { stj_set_error("stj_nadam_apply: null pointer"); return STJ_EINVAL; }
+  if ((((uintptr_t)w) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)coef)) & 15) {
+    stj_set_error("stj_nadam_apply: buffers must be 16-byte aligned"); return STJ_EINVAL;
+  }
+  long long b = (n / 4 + 255) / 256;
+  const int grid = (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
+  hipLaunchKernelGGL(nadam_apply_kernel, dim3(grid), dim3(256), 0, stream, w, g, m, v, n, coef, b1, b2, eps);
+  return stj_check_launch("stj_nadam_apply");
+}

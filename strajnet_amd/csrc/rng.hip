@@ -7,6 +7,7 @@
 // from (seed, step, site), and stj_dropout_mask exports it so the tests can hand the very same masks to the oracle.
 // `state` is a device int64[2] = {seed, step}; stj_rng_advance bumps step on the stream (hipGraph replays get fresh masks).
 #include "common.h"
+#include "nadam.h"
 #include "rng.h"
 
 // one draw per element: a thread owns 4 consecutive elements == one Philox block
@@ -151,20 +152,12 @@ __global__ __launch_bounds__(256) void nadam_kernel(float* __restrict__ w, const
     float4 M = reinterpret_cast<float4*>(m)[i], V = reinterpret_cast<float4*>(v)[i];
     float* wp = &W.x; float* gp = &G.x; float* mp = &M.x; float* vp = &V.x;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float gg = gp[e] * gscale;
-      mp[e] = b1 * mp[e] + (1.f - b1) * gg;
-      vp[e] = b2 * vp[e] + (1.f - b2) * gg * gg;
-      wp[e] -= lr * (cg * gg + cm * mp[e]) / (sqrtf(vp[e] * vhat_scale) + eps);
-    }
+    for (int e = 0; e < 4; ++e) nadam_update(wp[e], gp[e], mp[e], vp[e], lr, b1, b2, eps, cg, cm, vhat_scale, gscale);
     reinterpret_cast<float4*>(w)[i] = W; reinterpret_cast<float4*>(m)[i] = M; reinterpret_cast<float4*>(v)[i] = V;
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const long long i = nv * 4 + threadIdx.x;
-    const float gg = g[i] * gscale;
-    m[i] = b1 * m[i] + (1.f - b1) * gg;
-    v[i] = b2 * v[i] + (1.f - b2) * gg * gg;
-    w[i] -= lr * (cg * gg + cm * m[i]) / (sqrtf(v[i] * vhat_scale) + eps);
+    nadam_update(w[i], g[i], m[i], v[i], lr, b1, b2, eps, cg, cm, vhat_scale, gscale);
   }
 }
 // cg = (1 - mu_t) / (1 - prod_t), cm = mu_{t+1} / (1 - prod_{t+1}), vhat_scale = 1 / (1 - b2^t); gscale multiplies g first (e.g. 1).

@@ -17,12 +17,23 @@ class GraphedTrainStep:
     """split=False: ONE graph for the whole step.  split=True (data parallel): TWO graphs cut at the raster encoder's outputs
     (model.cut_encoder) -- graph A = forward + loss + backward of everything downstream of the encoder, graph B = the encoder's
     backward; `__call__(between=f)` runs f between the two replays (dp.OverlappedGradSync.tail: the tail bucket's all-reduce then
-    overlaps graph B).  Both graphs share one private memory pool: B reads the activations A saved."""
+    overlaps graph B).  Both graphs share one private memory pool: B reads the activations A saved.
 
-    def __init__(self, model, loss_fn, batch, warmup=2, training=True, split=False, keep_graph=False):
+    optimizer (an optim.DeviceNadam: its scalar state lives on the device): the update is captured at the end of the step, so one replay
+    is the whole of train.py:199-230 -- forward, loss, backward, update, and with optimizer.attach_loss_means the four train-loss means
+    (fed by each pass's LossDict.packed).  The warm-up passes do not train: weights, moments, optimizer state and running sums are put
+    back afterwards, bit for bit.  Not with split=True: the update must follow the all-reduce, which stays outside the graph."""
+
+    def __init__(self, model, loss_fn, batch, warmup=2, training=True, split=False, keep_graph=False, optimizer=None):
         """keep_graph: leave the captured hipGraph_t un-instantiated (torch.cuda.CUDAGraph(keep_graph=True)) so that a caller can edit it
         (self.graph.raw_cuda_graph(): e.g. kernel-node attributes, tools/probes/graph_node_priority.py) before self.graph.instantiate()."""
-        self.model, self.loss_fn, self.training, self.split = model, loss_fn, training, split
+        if optimizer is not None and split:
+            raise ValueError('GraphedTrainStep: optimizer= cannot be captured with split=True (the update must follow the all-reduce, '
+                             'which stays outside the graph): call optimizer.step() after sync.head_and_wait()')
+        if optimizer is not None and not getattr(optimizer, 'capturable', False):
+            raise ValueError('GraphedTrainStep: optimizer= needs an optimizer whose step() is launches only (optim.DeviceNadam); a '
+                             'host-state optimizer\'s coefficients would freeze at capture time')
+        self.model, self.loss_fn, self.training, self.split, self.optimizer = model, loss_fn, training, split, optimizer
         self.static = {k: v.clone() for k, v in batch.items()}
         self.graph = self.graph_b = None
         self._side = None
@@ -34,6 +45,8 @@ class GraphedTrainStep:
             loss_fn.unit_grad = self._one
         if split:
             model.cut_encoder = True
+        trained = optimizer.tensors() if optimizer is not None else []
+        snap = [t.clone() for t in trained]          # the warm-up passes must not train
         side = ops.role_stream(torch.cuda.current_device(), 'warmup')
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -41,6 +54,10 @@ class GraphedTrainStep:
                 self._eager()
                 if split:
                     model.backward_encoder()
+            for t, s in zip(trained, snap):
+                t.copy_(s)
+            if trained:
+                model._sync_compute_weights()        # the compute-dtype copy was cast from the warm-up's weights
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph(keep_graph=True) if keep_graph else torch.cuda.CUDAGraph()
@@ -79,6 +96,10 @@ class GraphedTrainStep:
         total = d.total                      # observed_xe + occluded_xe + flow + flow_warp_xe (train.py:221)
         total.backward(self._one)             # (an explicit tensor: backward()'s implicit ones_like is a fill launch on every replay)
         self.total = total.detach()           # the sum the finalize kernel wrote (static across replays, like self.losses)
+        if self.optimizer is not None:
+            if self.optimizer.loss_scale is not None:
+                self.optimizer.attach_loss_means(d.packed, self.optimizer.loss_scale)
+            self.optimizer.step()
         return d.packed             # [observed_xe, occluded_xe, flow, flow_warp_xe], detached
 
     def load(self, batch):

@@ -224,6 +224,7 @@ MODELS = {
     'stj_loss_fwd': _loss('loss_fwd', 1), 'stj_loss_bwd': _loss('loss_bwd', 2), 'stj_loss_fwd_bwd': _loss('loss_fwd_bwd', 2),
     'stj_eval_fwd': _eval,
     'stj_nadam_step': _elem('nadam', 4, 0, 7, f32=True),
+    'stj_gradnorm_partials': _elem('gradnorm', 1, 0, 1, f32=True), 'stj_nadam_apply': _elem('nadam_apply', 4, 0, 7, f32=True),
 }
 EXTRA_MODELS = {}        # fused kernels register their models here (ops.py)
 

@@ -1,0 +1,101 @@
+#!/usr/bin/env python
+"""What taking the optimizer into the captured train step costs or buys, measured with device events after warm-up, in
+one process: the replayed B = 8 bf16 cfg-256 train step (bench.py's headline workload) in three forms, each on a model of its own
+with the same seeds,
+
+  host     graph.GraphedTrainStep replay + optim.Nadam.step() issued by the host behind it (coefficients computed in Python);
+  device   GraphedTrainStep(optimizer=optim.DeviceNadam(...)) with defaults: the replay is the whole step (2 optimizer launches);
+  guarded  the same with global_clipnorm and skip_nonfinite (3 optimizer launches: the gradient's sum of squares first) and the
+           train-loss means kept by the prepare launch.
+
+Per round each form is timed once over --calls steps, the three alternating over --rounds rounds; the spread of the host form's own
+runs ((max - min) / median) is measured in the same call and is the margin of `not_slower`.  No threshold is set in advance: the
+JSON line reports the ratios.  Every device step runs inside this one process; run it under `timeout`."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ap = argparse.ArgumentParser()
+ap.add_argument('--batch', type=int, default=8)
+ap.add_argument('--calls', type=int, default=30, help='steps per timed run')
+ap.add_argument('--warmup', type=int, default=5)
+ap.add_argument('--rounds', type=int, default=3)
+ap.add_argument('--clipnorm', type=float, default=1.0e4)
+ap.add_argument('--out', default=None, help='append the JSON line to this file as well')
+a = ap.parse_args()
+
+import torch
+
+import bench
+from strajnet_amd import STrajNet, OGMFlow_loss, OccupancyFlowTaskConfig, Nadam, DeviceNadam
+from strajnet_amd.graph import GraphedTrainStep
+
+assert torch.cuda.is_available(), 'bench_train.py needs a GPU'
+dev = torch.device('cuda', 0)
+torch.cuda.set_device(dev)
+x = bench.synth_batch(a.batch, 1234, dev)
+
+
+def timed(fn, calls):
+    """ms per call of `calls` back-to-back calls between two device events."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(calls):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / calls
+
+
+def build(form):
+    model = STrajNet(bench.CFG256, fg_msa=True, fg=True, large_ogm=False, dtype=torch.bfloat16, device=dev, seed=0, dropout_seed=0)
+    loss_fn = OGMFlow_loss(OccupancyFlowTaskConfig(256, 256, 8), ogm_weight=1000.0, occ_weight=1000.0, flow_weight=1.0, replica=1.0,
+                           flow_origin_weight=1000.0, no_use_warp=False, use_pred=False, use_focal_loss=False, use_gt=True)
+    if form == 'host':
+        opt = Nadam.for_model(model, lr=1e-4)
+        graphed = GraphedTrainStep(model, loss_fn, x)
+
+        def step():
+            graphed()
+            opt.step()
+        return step, opt, model
+    kw = dict(global_clipnorm=a.clipnorm, skip_nonfinite=True) if form == 'guarded' else {}
+    opt = DeviceNadam.for_model(model, lr=1e-4, **kw)
+    if form == 'guarded':
+        opt.attach_loss_means(None, loss_fn.replica)
+    return GraphedTrainStep(model, loss_fn, x, optimizer=opt), opt, model
+
+
+forms = ('host', 'device', 'guarded')
+built = {f: build(f) for f in forms}
+for f in forms:
+    for _ in range(a.warmup):
+        built[f][0]()
+torch.cuda.synchronize()
+runs = {f: [] for f in forms}
+for _ in range(a.rounds):
+    for f in forms:
+        runs[f].append(timed(built[f][0], a.calls))
+torch.cuda.synchronize()
+med = {f: statistics.median(runs[f]) for f in forms}
+spread = (max(runs['host']) - min(runs['host'])) / med['host']
+guarded = built['guarded'][1]
+d = dict(tool='bench_train', batch=a.batch, calls=a.calls, rounds=a.rounds, clipnorm=a.clipnorm,
+         ms={f: round(med[f], 4) for f in forms}, runs={f: [round(v, 4) for v in runs[f]] for f in forms},
+         host_spread=round(spread, 4), steps_per_s={f: round(1e3 / med[f], 2) for f in forms})
+for f in ('device', 'guarded'):
+    d[f + '_ratio'] = round(med[f] / med['host'], 4)
+    d[f + '_not_slower'] = bool(med[f] <= med['host'] * (1.0 + spread))
+d.update(iterations={f: float(built[f][1].iterations) for f in ('device', 'guarded')}, host_iterations=built['host'][1].t,
+         skipped=float(guarded.skipped), grad_norm=float(guarded.grad_norm), loss_means=guarded.loss_result(),
+         weights_finite={f: bool(torch.isfinite(built[f][2].flat_weights()).all()) for f in forms})
+line = json.dumps(d)
+print(line, flush=True)
+if a.out:
+    with open(a.out, 'a') as fh:
+        fh.write(line + '\n')
