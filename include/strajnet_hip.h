@@ -522,6 +522,23 @@ int stj_unpack_bits(const uint32_t* bits, float* dst, long long n_total, hipStre
 int stj_unpack_sparse(const uint32_t* mask, const uint32_t* offs, const uint32_t* val_base, const float* vals, long long n_vals,
                       float* dst, int B, long long n, hipStream_t stream);
 
+/* Batches gathered from a pool of N packed scenes that stays on the device (csrc/pool.hip; the format is stated by PoolLayout.reference_gather
+ * in strajnet_amd/data.py).  idx: int32 [B] ON THE DEVICE, read by the kernel; scene b of dst (f32 [B][n]) is pool scene
+ * clamp(idx[b], 0, N - 1), so no index value reads outside the pool.
+ * stj_gather_bits: pool uint32 [N][n / 32]; the scene as stj_unpack_bits expands it.
+ * stj_gather_sparse: mask uint32 [N][n / 32], offs uint32 [N][ceil(n / 8192) + 1] (relative to the scene), val_base int64 [N + 1] (a pool's
+ * value words can pass 2^32), vals [n_vals]; the scene as stj_unpack_sparse expands it.  Gather indices are clamped to n_vals - 1; nothing is
+ * gathered when n_vals == 0.
+ * stj_gather_raw: pool [N][n] elements of `kind` as in stj_decode_raw; dst[b][i] = scale * cast(pool[idx[b]][i]), the bits of stj_decode_raw
+ * without a crop.  Any n >= 0, pool aligned to its element size.
+ * STJ_EUNSUPPORTED: n % 32 != 0 (bits, sparse), n >= 2^32, N < 1 with B > 0, misaligned pointers (4-byte streams and idx, 8-byte val_base,
+ * 16-byte dst), more workgroups than a launch takes; STJ_OK with nothing launched for B == 0.  One launch each on `stream`: no host
+ * synchronisation, no allocation, no atomics. */
+int stj_gather_bits(const uint32_t* pool, const int* idx, int N, float* dst, int B, long long n, hipStream_t stream);
+int stj_gather_sparse(const uint32_t* mask, const uint32_t* offs, const long long* val_base, const float* vals, long long n_vals,
+                      const int* idx, int N, float* dst, int B, long long n, hipStream_t stream);
+int stj_gather_raw(const void* pool, int kind, const int* idx, int N, float* dst, int B, long long n, float scale, hipStream_t stream);
+
 /* trajNet input plumbing (trajNet.py:125-140), one launch: obs [B,n_obs,Tn,8] and occ [B,n_occ,Tn,8] (f32, 16-byte aligned) ->
  * x5 [B*A*Tn,5] node features, v3 [B*A,3] vector features of step 0, vt [B*A,Tn] int32 step-valid (feature 0 != 0), cmi [B*A] int32 /
  * cmf [B*A] (type T) agent-valid (any step valid); A = n_obs + n_occ, obs rows first. */

@@ -1,5 +1,6 @@
 // Error plumbing + streaming elementwise kernels (HBM-bound: 16-byte vector access, grid-stride).
 #include "common.h"
+#include "rawcast.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -267,12 +268,7 @@ __global__ __launch_bounds__(256) void decode_raw_kernel(const void* __restrict_
     const int x = (int)(t % Wo); t /= Wo;
     const int y = (int)(t % Ho); const long long n = t / Ho;
     const long long s = ((n * H + y0 + y) * W + x0 + x) * C + c;
-    float v;
-    if constexpr (KIND == 0) v = reinterpret_cast<const unsigned char*>(src)[s] != 0 ? 1.f : 0.f;
-    else if constexpr (KIND == 1) v = (float)reinterpret_cast<const signed char*>(src)[s];
-    else if constexpr (KIND == 2) v = reinterpret_cast<const float*>(src)[s];
-    else v = (float)reinterpret_cast<const double*>(src)[s];
-    dst[i] = v * scale;
+    dst[i] = raw_to_f32<KIND>(src, s) * scale;
   }
 }
 extern "C" int stj_decode_raw(const void* src, int kind, float* dst, long long n_outer, int H, int W, int C, int y0, int x0, int Ho,

@@ -15,6 +15,10 @@ one bit per cell plus its non-zero words.  `pack_example` rewrites a parsed reco
 (`pack_bits`, `pack_sparse`; `unpack_reference` states the format and is the only CPU path); `decode_batch_packed` and `PackedFeed` upload
 the packed bytes and expand them on the device (stj_unpack_bits / stj_unpack_sparse) into the same float32 tensors, bit for bit, that
 `decode_batch` and `HostFeed.land()` give for the original record.
+
+Scenes resident in HBM (opt-in): `PoolLayout` lays N packed scenes out for the device, `ResidentPool` uploads them once, and batches are
+gathered from them by a device index vector (stj_gather_bits / stj_gather_sparse / stj_gather_raw) -- `ResidentFeed` has HostFeed's protocol
+with no upload per step, `PoolSampler` shuffles on the device.  `PoolLayout.reference_gather` states the semantics in NumPy.
 """
 import ctypes
 import struct
@@ -722,3 +726,363 @@ class PackedFeed(HostFeed):
     def upload_bytes(self):
         """Bytes the next upload moves, as the host buffers stand."""
         return sum(h.numel() * h.element_size() for h in self.host.values()) + sum(sh.nbytes for sh in self.sparse.values())
+
+
+# ---------------------------------------------------------------------------------------------------- scenes resident in HBM
+_KIND_NAME = {v: k for k, v in KIND.items()}
+POOL_NAMES = {'ogm': 'ogm', 'map_image': 'map_img', 'actors': 'obs', 'occl_actors': 'occ', 'centerlines': 'mapt', 'vec_flow': 'flow',
+              'gt_obs_ogm': 'gt_obs', 'gt_occ_ogm': 'gt_occ', 'gt_flow': 'gt_flow', 'origin_flow': 'origin_flow'}
+
+
+def _scene_words(x):
+    """uint32 words of an array or of a record's bytes; None unless whole 32-bit words."""
+    b = np.ascontiguousarray(x).reshape(-1).view(np.uint8) if isinstance(x, np.ndarray) else np.frombuffer(bytes(x), np.uint8)
+    return None if b.size % 4 else b.view('<u4')
+
+
+class PoolLayout:
+    """N packed scenes laid out as stj_gather_bits / stj_gather_sparse / stj_gather_raw read them; NumPy only, no device.
+
+    A key (any string; PackedFeed and ResidentFeed work on the keys of a step's `static` dict) holds one feature of every scene:
+      bits    words  uint32 [N, n / 32] in pack_bits' order;
+      sparse  mask   uint32 [N, n / 32], offs uint32 [N, ceil(n / SPARSE_BLOCK) + 1] relative to the scene, val_base int64 [N + 1] the running
+              total of the scenes' value words (64-bit: a pool's can pass 2^32 although a batch's cannot), vals uint32 [val_base[-1]];
+      raw     the record's own elements [N, n] (bool / int8 / float32 / float64) and the scale of feature_spec.
+    Every key holds the same number of scenes.  Malformed streams, scenes of differing size, a key added twice and differing scene counts
+    raise ValueError naming the key and the scene.  reference_gather states what the kernels compute."""
+
+    def __init__(self):
+        self.entries = {}          # key -> {'kind': 'bits' | 'sparse' | 'raw', 'n', 'shape', arrays ...}
+        self.N = None
+
+    def _begin(self, key, scenes):
+        if key in self.entries:
+            raise ValueError(f'PoolLayout[{key!r}]: key added twice')
+        scenes = list(scenes)
+        if self.N is not None and len(scenes) != self.N:
+            raise ValueError(f'PoolLayout[{key!r}]: {len(scenes)} scenes where the other keys hold {self.N}: '
+                             f'scene {min(len(scenes), self.N)} is the first without a partner')
+        if not scenes:
+            raise ValueError(f'PoolLayout[{key!r}]: no scene 0: an empty pool')
+        return scenes
+
+    def _end(self, key, N, n, shape, entry):
+        shape = (n,) if shape is None else tuple(int(s) for s in shape)
+        if int(np.prod(shape)) != n:
+            raise ValueError(f'PoolLayout[{key!r}]: shape {shape} does not hold the {n} elements of scene 0')
+        if n >= 1 << 32:
+            raise ValueError(f'PoolLayout[{key!r}]: scene 0 has {n} elements, fewer than 2^32 only')
+        self.entries[key] = dict(entry, n=n, shape=shape)
+        self.N = N
+
+    def add_bits(self, key, scenes, shape=None):
+        """scenes: per scene the pack_bits words (uint32 array) or the record's `<name>/bits` bytes; n = 32 x the words of scene 0."""
+        scenes = self._begin(key, scenes)
+        words = []
+        for i, s in enumerate(scenes):
+            w = _scene_words(s)
+            if w is None:
+                raise ValueError(f'PoolLayout[{key!r}] scene {i}: bits are not whole 32-bit words')
+            if words and w.size != words[0].size:
+                raise ValueError(f'PoolLayout[{key!r}] scene {i}: {w.size} words, scene 0 has {words[0].size}')
+            words.append(w)
+        self._end(key, len(words), 32 * words[0].size, shape, {'kind': 'bits', 'words': np.stack(words).astype(np.uint32)})
+        return self
+
+    def add_sparse(self, key, scenes, n, shape=None):
+        """scenes: per scene (mask, offs, vals) of n elements, arrays or the record's bytes; each checked with check_sparse."""
+        scenes = self._begin(key, scenes)
+        planes = []
+        for i, s in enumerate(scenes):
+            try:
+                planes.append(check_sparse(*s, n, 'stream'))
+            except (ValueError, TypeError) as e:
+                raise ValueError(f'PoolLayout[{key!r}] scene {i}: {e}') from None
+        base = np.zeros(len(planes) + 1, np.int64)
+        base[1:] = np.cumsum([p[2].size for p in planes], dtype=np.int64)
+        vals = np.concatenate([p[2] for p in planes]).astype(np.uint32)
+        self._end(key, len(planes), int(n), shape, {'kind': 'sparse', 'mask': np.stack([p[0] for p in planes]).astype(np.uint32),
+                                       'offs': np.stack([p[1] for p in planes]).astype(np.uint32), 'val_base': base, 'vals': vals})
+        return self
+
+    def add_raw(self, key, scenes, kind, scale=1.0, shape=None):
+        """scenes: per scene the record's own elements, an array or bytes; kind: 'bool' / 'int8' / 'float32' / 'float64' or its code."""
+        kind = _KIND_NAME.get(kind, kind)
+        if kind not in KIND:
+            raise ValueError(f'PoolLayout[{key!r}]: raw kind {kind!r}')
+        scenes = self._begin(key, scenes)
+        rows = []
+        for i, s in enumerate(scenes):
+            b = np.ascontiguousarray(s).reshape(-1).view(np.uint8) if isinstance(s, np.ndarray) else np.frombuffer(bytes(s), np.uint8)
+            if b.size % ITEMSIZE[kind]:
+                raise ValueError(f'PoolLayout[{key!r}] scene {i}: {b.size} bytes are not whole {kind} elements')
+            if rows and b.size != rows[0].size:
+                raise ValueError(f'PoolLayout[{key!r}] scene {i}: {b.size} bytes, scene 0 has {rows[0].size}')
+            rows.append(b)
+        data = np.stack(rows).view(_RAW_DTYPE[kind])
+        self._end(key, len(rows), data.shape[1], shape, {'kind': 'raw', 'data': data, 'dtype': kind, 'scale': float(scale)})
+        return self
+
+    @classmethod
+    def from_examples(cls, packed_examples, grid=512, out=256, test=False, names=None):
+        """The layout of a list of pack_example records.  The packed features go in as packed, the others as the record's own bytes
+        (map_image stays int8 with scale 1/256, the float64 agent arrays stay float64); a record that is not packed at all is accepted and
+        stored raw, a ground-truth feature after its centre crop.  names: record name -> key; the default maps to the keys of a step's
+        `static` dict (POOL_NAMES).  'scenario/id' is not a tensor and stays with the caller."""
+        names = POOL_NAMES if names is None else names
+        exs = list(packed_examples)
+        self = cls()
+        for name, (dtype, shape, crop, scale) in feature_spec(grid, out, test).items():
+            key = names.get(name, name)
+            dshape = decoded_shape(shape, crop)
+            n = int(np.prod(dshape))
+            kind = PACKED_KIND.get(name)
+            try:
+                if kind == 'bits' and exs and name + '/bits' in exs[0]:
+                    self.add_bits(key, [ex[name + '/bits'] for ex in exs], dshape)
+                    if self.entries[key]['n'] != n:
+                        raise ValueError(f"PoolLayout[{key!r}] scene 0: {self.entries[key]['n']} bits, expected {n}")
+                elif kind == 'sparse' and exs and name + '/mask' in exs[0]:
+                    self.add_sparse(key, [tuple(ex[f'{name}/{p}'] for p in ('mask', 'offs', 'vals')) for ex in exs], n, dshape)
+                else:
+                    rows = []
+                    for i, ex in enumerate(exs):
+                        try:
+                            rows.append(np.ascontiguousarray(_decoded(ex[name], dtype, shape, crop)))
+                        except ValueError as e:
+                            raise ValueError(f'PoolLayout[{key!r}] scene {i}: {e}') from None
+                    self.add_raw(key, rows, dtype, scale, dshape)
+            except KeyError as e:
+                raise ValueError(f'PoolLayout[{key!r}]: a scene lacks the record feature {e}') from None
+        return self
+
+    def check_index(self, idx):
+        """A host index list: ValueError unless every index is in [0, N).  -> int64 array."""
+        idx = np.asarray(idx, np.int64).reshape(-1)
+        bad = np.flatnonzero((idx < 0) | (idx >= self.N))
+        if bad.size:
+            raise ValueError(f'pool index {int(idx[bad[0]])} at position {int(bad[0])} is outside the {self.N} scenes')
+        return idx
+
+    def reference_gather(self, idx):
+        """The semantics of the gather kernels in NumPy, built on unpack_reference: {key: float32 [B, ...]}, scene b of every key being
+        pool scene clamp(idx[b], 0, N - 1) -- the kernels clamp, so that no index reads outside the pool."""
+        idx = np.clip(np.asarray(idx, np.int64).reshape(-1), 0, self.N - 1)
+        res = {}
+        for key, e in self.entries.items():
+            rows = []
+            for s in idx:
+                if e['kind'] == 'bits':
+                    r = unpack_reference('bits', e['words'][s], e['n'])
+                elif e['kind'] == 'sparse':
+                    r = unpack_reference('sparse', e['mask'][s], e['offs'][s], e['vals'][e['val_base'][s]:e['val_base'][s + 1]], e['n'])
+                else:
+                    a = e['data'][s]
+                    a = a.view(np.float32) if e['dtype'] == 'float32' else (a != 0) if e['dtype'] == 'bool' else a
+                    r = a.astype(np.float32) * np.float32(e['scale'])
+                rows.append(r.reshape(e['shape']))
+            res[key] = np.stack(rows) if rows else np.zeros((0,) + e['shape'], np.float32)
+        return res
+
+    def arrays(self, key):
+        """The arrays of a key that go to the device, by name."""
+        e = self.entries[key]
+        return {p: e[p] for p in {'bits': ('words',), 'sparse': ('mask', 'offs', 'val_base', 'vals'), 'raw': ('data',)}[e['kind']]}
+
+    @property
+    def nbytes(self):
+        """Bytes the pool occupies on the device."""
+        return sum(a.nbytes for key in self.entries for a in self.arrays(key).values())
+
+
+class PoolSampler:
+    """Endless iterator over batches of pool indices: int32 tensors on `device`, made there, never synchronising with the host.  With
+    shuffle every epoch is torch.randperm(N) of the sampler's own generator cut into batches -- a full permutation of the resident scenes,
+    not the reference's 64-scene shuffle buffer (train.py:381); without, the scenes run in order.  drop_last=False keeps the shorter last
+    batch of an epoch (ResidentPool.gather takes it, ResidentFeed.land refuses it).  Under data parallelism each rank builds its pool
+    from its own share of the records and shuffles within it.  epoch() returns the batches of the next whole epoch."""
+
+    def __init__(self, N, batch_size, device='cuda', shuffle=True, seed=0, drop_last=True):
+        if N < 1 or batch_size < 1 or (drop_last and batch_size > N):
+            raise ValueError(f'PoolSampler: no batch of {batch_size} out of {N} scenes')
+        self.N, self.batch_size, self.shuffle, self.drop_last = int(N), int(batch_size), shuffle, drop_last
+        self.device = torch.device(device)
+        self.gen = torch.Generator(device=self.device).manual_seed(int(seed))
+        self._order = None if shuffle else torch.arange(self.N, dtype=torch.int32, device=self.device)
+        self._todo = []
+
+    def __len__(self):
+        return self.N // self.batch_size if self.drop_last else -(-self.N // self.batch_size)
+
+    def epoch(self):
+        order = torch.randperm(self.N, dtype=torch.int32, device=self.device, generator=self.gen) if self.shuffle else self._order
+        self._todo = []
+        return list(order.split(self.batch_size))[:len(self)]
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if not self._todo:
+            self._todo = self.epoch()[::-1]
+        return self._todo.pop()
+
+
+class ResidentPool:
+    """A PoolLayout uploaded once and kept in HBM; batches are gathered from it by an index vector that lives on the device
+    (stj_gather_bits / stj_gather_sparse / stj_gather_raw: one launch per key, no upload, no worker thread).
+
+        pool = ResidentPool(PoolLayout.from_examples(packed, grid, out, test), 'cuda')
+        batch = pool.gather(idx)                 # the dict decode_batch_packed gives for those scenes (keys: the layout's)
+        pool.gather_into(step.static, idx)       # into existing tensors; keys the pool does not hold stay untouched
+
+    The upload goes through pinned staging on the process's one copy stream in pieces of chunk_bytes (HostFeed explains why one large copy
+    is wrong while a step is running); an event marks it done and the first gather waits on it.  idx: a device int32 tensor, trusted
+    because the kernels clamp it to the pool, or a host list, range-checked (ValueError).
+    Out of scope: a pool is immutable once built.  Replacing scenes in place, or a rolling window over a dataset larger than HBM, is not
+    built; a caller that needs more builds a second pool while the first is in use."""
+
+    def __init__(self, layout, device='cuda', chunk_bytes=3 << 19):
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise RuntimeError('ResidentPool: CUDA (ROCm) device only: the HIP path has no CPU fallback')
+        if not layout.entries:
+            raise ValueError('ResidentPool: an empty layout')
+        self.layout, self.dev, self.N = layout, dev, layout.N
+        self.dev_arrays, self._staging = {}, []
+        copy = _copy_stream(dev)
+        self.up = torch.cuda.Event()
+        chunk = max(1, int(chunk_bytes))
+        with torch.cuda.stream(copy):
+            for key in layout.entries:
+                self.dev_arrays[key] = {}
+                for part, a in layout.arrays(key).items():
+                    nb = a.nbytes
+                    host = torch.empty((max(nb, 8),), dtype=torch.uint8).pin_memory()
+                    host.numpy()[:nb] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+                    d = torch.empty((max(nb, 8),), dtype=torch.uint8, device=dev)          # never empty: a real pointer
+                    for i in range(0, nb, chunk):
+                        d[i:i + chunk].copy_(host[i:i + chunk], non_blocking=True)
+                    self._staging.append(host)
+                    self.dev_arrays[key][part] = d
+            self.up.record(copy)
+        self._ready = False
+
+    @classmethod
+    def from_examples(cls, packed_examples, device='cuda', grid=512, out=256, test=False, names=None, chunk_bytes=3 << 19):
+        return cls(PoolLayout.from_examples(packed_examples, grid, out, test, names), device, chunk_bytes)
+
+    @property
+    def nbytes(self):
+        return self.layout.nbytes
+
+    def wait(self):
+        """Host-side: returns once the upload has finished (call it before capturing gathers in a graph)."""
+        self.up.synchronize()
+        self._ready, self._staging = True, []
+
+    def _await_upload(self):
+        if self._ready:
+            return
+        if self.up.query():
+            self._ready, self._staging = True, []
+        elif torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('ResidentPool: the upload has not finished; call pool.wait() before capturing a gather')
+        else:
+            torch.cuda.current_stream(self.dev).wait_event(self.up)
+
+    def index(self, idx):
+        """idx as the kernels take it: a device int32 tensor is trusted (the kernels clamp); a host list is range-checked and copied."""
+        if isinstance(idx, torch.Tensor) and idx.is_cuda:
+            if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous():
+                raise ValueError(f'pool index: a contiguous int32 [B] device tensor only, got {idx.dtype} {tuple(idx.shape)}')
+            return idx
+        host = self.layout.check_index(idx.tolist() if isinstance(idx, torch.Tensor) else idx)
+        return torch.from_numpy(host.astype(np.int32)).to(self.dev)
+
+    def _launch(self, key, dst, idx):
+        e, d = self.layout.entries[key], self.dev_arrays[key]
+        B, n = idx.numel(), e['n']
+        if e['kind'] == 'bits':
+            call('stj_gather_bits', _p(d['words']), _p(idx), self.N, _p(dst), B, n, _st())
+        elif e['kind'] == 'sparse':
+            call('stj_gather_sparse', _p(d['mask']), _p(d['offs']), _p(d['val_base']), _p(d['vals']), int(e['val_base'][-1]), _p(idx), self.N,
+                 _p(dst), B, n, _st())
+        else:
+            call('stj_gather_raw', _p(d['data']), KIND[e['dtype']], _p(idx), self.N, _p(dst), B, n, e['scale'], _st())
+
+    def gather(self, idx):
+        """-> {key: float32 [B, ...]} freshly allocated: what decode_batch_packed returns for the scenes idx."""
+        idx = self.index(idx)
+        self._await_upload()
+        res = {}
+        for key, e in self.layout.entries.items():
+            res[key] = torch.empty((idx.numel(),) + e['shape'], dtype=torch.float32, device=self.dev)
+            self._launch(key, res[key], idx)
+        return res
+
+    def gather_into(self, static, idx):
+        """The same into the tensors of `static` (float32, contiguous, [B] + the key's shape); keys the pool does not hold are left alone."""
+        idx = self.index(idx)
+        todo = self.check_static(static, idx.numel())
+        self._await_upload()
+        for key in todo:
+            self._launch(key, static[key], idx)
+
+    def check_static(self, static, B):
+        """ValueError unless every tensor of `static` under a key of the pool is what a gather of B scenes writes.  -> those keys."""
+        todo = [key for key in self.layout.entries if key in static]
+        for key in todo:
+            t, want = static[key], (B,) + self.layout.entries[key]['shape']
+            if t.dtype != torch.float32 or tuple(t.shape) != want or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError(f'ResidentPool: static[{key!r}] is {t.dtype} {tuple(t.shape)} on {t.device}, expected contiguous float32 {want} on {self.dev}')
+        return todo
+
+    def sampler(self, batch_size, shuffle=True, seed=0, drop_last=True):
+        """PoolSampler over this pool's scenes, on its device."""
+        return PoolSampler(self.N, batch_size, self.dev, shuffle, seed, drop_last)
+
+
+class ResidentFeed:
+    """HostFeed's protocol (start / land / wait_uploaded / close) over a ResidentPool: nothing is uploaded per step, so there is no worker
+    thread and wait_uploaded() returns at once.  Works on GraphedTrainStep.static, GraphedForward.static and GraphedEvalStep.static.
+
+        feed = ResidentFeed(step.static, pool)
+        feed.start()
+        for ...:
+            feed.land()                    # next batch of the feed's sampler; or feed.land(idx)
+            step(); optimizer.step()
+
+    feed.idx is a persistent device int32 [B] tensor: land(idx) copies idx into it on the current stream and launches the gathers, which
+    read feed.idx -- so a caller may capture the launches in a graph of their own and change feed.idx between replays.  The landing stays
+    in front of the step's replay, as HostFeed's does."""
+
+    def __init__(self, static, pool, sampler=None):
+        self.static, self.pool = static, pool
+        keys = [k for k in pool.layout.entries if k in static]
+        if not keys:
+            raise ValueError('ResidentFeed: the pool holds none of the keys of `static`')
+        self.B = static[keys[0]].shape[0]
+        self.idx = torch.zeros((self.B,), dtype=torch.int32, device=pool.dev)
+        self.sampler = sampler
+        pool.check_static(static, self.B)
+
+    def start(self):
+        pass
+
+    def land(self, idx=None):
+        if idx is None:
+            if self.sampler is None:
+                self.sampler = self.pool.sampler(self.B)
+            idx = next(self.sampler)
+        idx = self.pool.index(idx)
+        if idx.numel() != self.B:
+            raise ValueError(f'ResidentFeed: {idx.numel()} indices for a static batch of {self.B}')
+        self.idx.copy_(idx, non_blocking=True)
+        self.pool.gather_into(self.static, self.idx)
+
+    def wait_uploaded(self):
+        return
+
+    def close(self):
+        pass

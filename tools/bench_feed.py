@@ -6,13 +6,15 @@
 
 Feed modes, all on the SAME captured graph in one process: `resident` (inputs stay in HBM, no feed), `f32` (HostFeed, decoded float32
 tensors), `raw` (HostFeed, the record's own bytes: bool grids and the int8 map one byte per element, float32 flows), `packed`
-(PackedFeed: bool grids one bit per element, flows as mask + non-zero words, int8 map).  Per visit every mode is timed TWICE in a row,
+(PackedFeed: bool grids one bit per element, flows as mask + non-zero words, int8 map), `pool` (ResidentFeed, DESIGN 4u: --pool-scenes x B
+blob scenes packed the same way stay in HBM, every step gathers a freshly sampled batch by device index, nothing is uploaded).  Per visit
+every mode is timed TWICE in a row,
 the modes alternating, --pairs visits: the spread of repeated runs of one mode is measured in the same call.  One JSON line per run:
 scenes/s, bytes uploaded per scene, the density of the synthetic scene.
 
   --all            runs both configs as child processes, each under its own `timeout`; --out FILE collects their lines
-  --trace          a few PackedFeed landings at the config's shapes and nothing else (no model): the workload of a
-                   `rocprofv3 --kernel-trace --stats` run; prints the bytes each kernel reads and writes per landing
+  --trace          a few PackedFeed and ResidentFeed landings at the config's shapes and nothing else (no model): the workload of a
+                   `rocprofv3 --kernel-trace --stats` run; prints the bytes each unpack / gather kernel reads and writes per landing
 
 The scenes are synthetic: --blobs rectangular vehicles per scene on a zero background, occupancy in every time step, flow non-zero only
 inside them (random-normal flow would be dense, and `sparse` then larger than raw).  Real Waymo densities are not available here.
@@ -29,13 +31,14 @@ sys.path.insert(0, ROOT)
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--config', default='train', choices=['train', 'infer'])
-ap.add_argument('--modes', default='resident,f32,raw,packed')
+ap.add_argument('--modes', default='resident,f32,raw,packed,pool')
 ap.add_argument('--steps', type=int, default=100)
 ap.add_argument('--warmup', type=int, default=10)
 ap.add_argument('--pairs', type=int, default=2)
 ap.add_argument('--batch', type=int, default=None)
 ap.add_argument('--blobs', type=int, default=24, help='vehicles per scene')
 ap.add_argument('--seed', type=int, default=1234)
+ap.add_argument('--pool-scenes', type=int, default=8, help='mode pool: the pool holds this many batches of scenes')
 ap.add_argument('--all', action='store_true')
 ap.add_argument('--trace', action='store_true')
 ap.add_argument('--timeout', type=int, default=420, help='--all: seconds per child')
@@ -55,7 +58,8 @@ if a.all:
     rc = 0
     for cfg in ('train', 'infer'):
         cmd = ['timeout', '-k', '10', str(a.timeout), sys.executable, os.path.abspath(__file__), '--config', cfg, '--modes', a.modes,
-               '--steps', str(a.steps), '--warmup', str(a.warmup), '--pairs', str(a.pairs), '--blobs', str(a.blobs), '--seed', str(a.seed)]
+               '--steps', str(a.steps), '--warmup', str(a.warmup), '--pairs', str(a.pairs), '--blobs', str(a.blobs), '--seed', str(a.seed),
+               '--pool-scenes', str(a.pool_scenes)]
         if a.out:
             cmd += ['--out', a.out]
         r = subprocess.run(cmd)
@@ -68,7 +72,8 @@ import numpy as np
 import torch
 
 import bench
-from strajnet_amd.data import HostFeed, PackedFeed, SparseHost, bits_host
+from strajnet_amd.data import (HostFeed, PackedFeed, PoolLayout, ResidentFeed, ResidentPool, SparseHost, bits_host, pack_bits,
+                               pack_sparse)
 
 assert torch.cuda.is_available(), 'bench_feed.py needs a GPU'
 dev = torch.device('cuda', 0)
@@ -131,6 +136,57 @@ def make_feed(mode, static, xh):
     return HostFeed(static, host, raw), sum(h.numel() * h.element_size() for h in host.values())
 
 
+def make_pool_feed(static):
+    """-> (ResidentFeed over a pool of --pool-scenes x B blob scenes under the keys of `static`, 0 bytes uploaded per batch).  The scenes
+    are drawn B at a time, so the host never holds more than one batch decoded."""
+    cols = {k: [] for k in xh if k in static}
+    for j in range(a.pool_scenes):
+        xj = blob_scenes(B, a.seed + 1 + j, a.blobs)
+        for k, col in cols.items():
+            v = xj[k].float().numpy()
+            if k in BITS:
+                col += [pack_bits(s) for s in v]
+            elif k in SPARSE:
+                col += [pack_sparse(s) for s in v]
+            elif k in INT8:
+                col += list(np.round(v * 256.0).astype(np.int8))
+            else:
+                col += list(v.view(np.uint32))
+    lay = PoolLayout()
+    for k, col in cols.items():
+        shape = tuple(static[k].shape[1:])
+        if k in BITS:
+            lay.add_bits(k, col, shape)
+        elif k in SPARSE:
+            lay.add_sparse(k, col, int(np.prod(shape)), shape)
+        elif k in INT8:
+            lay.add_raw(k, col, 'int8', 1.0 / 256.0, shape)
+        else:
+            lay.add_raw(k, col, 'float32', 1.0, shape)
+    pool = ResidentPool(lay, dev)
+    pool.wait()
+    return ResidentFeed(static, pool, pool.sampler(B, seed=a.seed)), 0
+
+
+def pool_bytes(feed):
+    """Per key: the kernel and the bytes the last landing read and wrote (the index, 4 B per scene, on top of every read)."""
+    idx = feed.idx.cpu().numpy()
+    per = {}
+    for k, e in feed.pool.layout.entries.items():
+        if k not in feed.static:
+            continue
+        n = e['n']
+        if e['kind'] == 'bits':
+            kernel, read = 'gather_bits_kernel', B * n // 8
+        elif e['kind'] == 'sparse':
+            present = int((e['val_base'][idx + 1] - e['val_base'][idx]).sum())
+            kernel, read = 'gather_sparse_kernel', B * (e['mask'].shape[1] + e['offs'].shape[1] + 2) * 4 + 4 * present
+        else:
+            kernel, read = 'gather_raw_kernel', B * n * e['data'].itemsize
+        per[k] = {'kernel': kernel, 'written_bytes': B * n * 4, 'read_bytes': read + 4 * B}
+    return per
+
+
 xh = blob_scenes(B, a.seed, a.blobs)
 density = {k: round(float((xh[k] != 0).float().mean()), 5) for k in BITS + SPARSE}
 
@@ -148,6 +204,12 @@ if a.trace:
                'read_bytes': (static[k].numel() // 8 if k in BITS else feed.sparse[k].nbytes)} for k in keys if k in BITS + SPARSE}
     emit({'mode': 'trace', 'config': a.config, 'batch': B, 'landings': 10, 'blobs': a.blobs, 'density': density,
           'upload_bytes_per_scene': nbytes / B, 'per_landing': per})
+    feed, _ = make_pool_feed(static)
+    for _ in range(10):
+        feed.land()
+    torch.cuda.synchronize()
+    emit({'mode': 'trace', 'feed': 'pool', 'config': a.config, 'batch': B, 'landings': 10, 'blobs': a.blobs, 'pool_scenes': feed.pool.N,
+          'pool_bytes_per_scene': feed.pool.nbytes / feed.pool.N, 'per_landing': pool_bytes(feed)})
     sys.exit(0)
 
 from strajnet_amd import STrajNet
@@ -192,7 +254,7 @@ def timed(feed):
 modes = a.modes.split(',')
 feeds = {}
 for m in modes:
-    feeds[m] = (None, 0) if m == 'resident' else make_feed(m, graphed.static, xh)
+    feeds[m] = (None, 0) if m == 'resident' else make_pool_feed(graphed.static) if m == 'pool' else make_feed(m, graphed.static, xh)
     if feeds[m][0] is not None:
         feeds[m][0].start()
 for visit in range(a.pairs):
@@ -202,7 +264,8 @@ for visit in range(a.pairs):
             dt = timed(feed)
             emit({'config': a.config, 'mode': m, 'visit': visit, 'rep': rep, 'batch': B, 'steps': a.steps, 'warmup': a.warmup,
                   'scenes_per_s': round(B * a.steps / dt, 1), 'ms_per_step': round(dt / a.steps * 1e3, 4),
-                  'upload_bytes_per_scene': round(nbytes / B), 'blobs': a.blobs, 'density': density})
+                  'upload_bytes_per_scene': round(nbytes / B), 'blobs': a.blobs, 'density': density,
+                  **({'pool_scenes': feed.pool.N, 'pool_bytes_per_scene': round(feed.pool.nbytes / feed.pool.N)} if m == 'pool' else {})})
 for feed, _ in feeds.values():
     if feed is not None:
         feed.wait_uploaded()
