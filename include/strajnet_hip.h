@@ -539,6 +539,36 @@ int stj_gather_sparse(const uint32_t* mask, const uint32_t* offs, const long lon
                       const int* idx, int N, float* dst, int B, long long n, hipStream_t stream);
 int stj_gather_raw(const void* pool, int kind, const int* idx, int N, float* dst, int B, long long n, float scale, hipStream_t stream);
 
+/* Raw record bytes packed on the device into the slots of such a pool (csrc/pack.hip; the semantics are stated by
+ * PoolLayout.replace_reference in strajnet_amd/data.py).  src: the record's own bytes of B scenes, [B][T][H][W][C] elements; decoded element i
+ * of a scene (n = T Ho Wo C of them) is source element (t, y0 + y, x0 + x, c) as in stj_decode_raw, uncropped T = H = C = 1, W = n.  slots:
+ * int32 [B] ON THE DEVICE, scene b goes to pool slot slots[b]; ok: int32 [B] on the device, 1 = the scene lands.  A scene with ok[b] == 0
+ * or a slot outside [0, N) is skipped by every entry point (never clamped); duplicate slots are the caller's error (the result is
+ * unspecified, every access stays inside the pool arrays).
+ * stj_pack_bits: src bool bytes (non-zero = set) -> pool_words uint32 [N][n / 32] in pack_bits' order.
+ * stj_pack_sparse_count: src float32 words, present iff the 32-bit pattern is non-zero -> offs_stage uint32 [B][ceil(n / 8192) + 1], the
+ * present words of every block of 8192 elements.
+ * stj_pool_admit (one launch per sparse key, between its count and the commits): offs_stage[b][0 .. nblk] becomes the exclusive prefix with the
+ * total at [nblk], in place; ok[b] = (first ? 0 <= slots[b] < N : ok[b]) && total <= val_base[s + 1] - val_base[s].  offs_stage NULL: the
+ * range check alone (a pool without a sparse key).
+ * stj_pack_sparse_commit: the slot's mask words uint32 [N][n / 32], its offs row [N][nblk + 1] (copied from offs_stage) and the present words
+ * at vals[val_base[s] + offs_stage[b][blk] + rank] in element order (-0.0, NaN payloads and denormals unchanged).  Index arithmetic into
+ * vals is 64-bit and every store is inside [val_base[s], min(val_base[s + 1], n_vals)), whatever offs_stage and val_base hold.
+ * stj_pool_put_raw: rows of n elements of `itemsize` (1, 4 or 8) bytes, src [B][n] -> pool [N][n]; any n >= 0, no crop.
+ * STJ_EUNSUPPORTED: n % 32 != 0 (bits, sparse), n >= 2^32, misaligned pointers (4-byte streams, slots and ok, 8-byte val_base, src / pool of
+ * stj_pool_put_raw to the element size), more workgroups than a launch takes; STJ_EINVAL: NULL, negative sizes, a crop outside the source;
+ * STJ_OK with nothing launched for B == 0.  One launch each on `stream`: no host synchronisation, no allocation, no atomics. */
+int stj_pack_bits(const uint8_t* src, const int* ok, const int* slots, int N, uint32_t* pool_words, int B, int T, int H, int W, int C, int y0,
+                  int x0, int Ho, int Wo, hipStream_t stream);
+int stj_pack_sparse_count(const float* src, uint32_t* offs_stage, int B, int T, int H, int W, int C, int y0, int x0, int Ho, int Wo,
+                          hipStream_t stream);
+int stj_pool_admit(uint32_t* offs_stage, int nblk, const long long* val_base, const int* slots, int N, int* ok, int B, int first,
+                   hipStream_t stream);
+int stj_pack_sparse_commit(const float* src, const uint32_t* offs_stage, const int* ok, const int* slots, int N, uint32_t* mask_pool,
+                           uint32_t* offs_pool, const long long* val_base, float* vals, long long n_vals, int B, int T, int H, int W, int C,
+                           int y0, int x0, int Ho, int Wo, hipStream_t stream);
+int stj_pool_put_raw(const void* src, int itemsize, const int* ok, const int* slots, int N, void* pool, int B, long long n, hipStream_t stream);
+
 /* trajNet input plumbing (trajNet.py:125-140), one launch: obs [B,n_obs,Tn,8] and occ [B,n_occ,Tn,8] (f32, 16-byte aligned) ->
  * x5 [B*A*Tn,5] node features, v3 [B*A,3] vector features of step 0, vt [B*A,Tn] int32 step-valid (feature 0 != 0), cmi [B*A] int32 /
  * cmf [B*A] (type T) agent-valid (any step valid); A = n_obs + n_occ, obs rows first. */

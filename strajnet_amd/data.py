@@ -19,6 +19,9 @@ the packed bytes and expand them on the device (stj_unpack_bits / stj_unpack_spa
 Scenes resident in HBM (opt-in): `PoolLayout` lays N packed scenes out for the device, `ResidentPool` uploads them once, and batches are
 gathered from them by a device index vector (stj_gather_bits / stj_gather_sparse / stj_gather_raw) -- `ResidentFeed` has HostFeed's protocol
 with no upload per step, `PoolSampler` shuffles on the device.  `PoolLayout.reference_gather` states the semantics in NumPy.
+Pool scenes are replaced in place from the reference's own unpacked records: `ResidentPool.empty` allocates zero-filled slots,
+`PoolWriter` (pool.writer(B)) uploads the raw bytes and packs them on the device (stj_pack_bits / stj_pack_sparse_count / stj_pool_admit /
+stj_pack_sparse_commit / stj_pool_put_raw); `PoolLayout.replace_reference` states that in NumPy.
 """
 import ctypes
 import struct
@@ -754,6 +757,8 @@ class PoolLayout:
     def __init__(self):
         self.entries = {}          # key -> {'kind': 'bits' | 'sparse' | 'raw', 'n', 'shape', arrays ...}
         self.N = None
+        self.geometry = None       # (grid, out, test, names) of from_examples / empty: what a PoolWriter needs to read raw records
+        self.device_only = False   # ResidentPool.empty: the entries hold 'parts' {name: (shape, dtype)} and no arrays
 
     def _begin(self, key, scenes):
         if key in self.entries:
@@ -789,8 +794,11 @@ class PoolLayout:
         self._end(key, len(words), 32 * words[0].size, shape, {'kind': 'bits', 'words': np.stack(words).astype(np.uint32)})
         return self
 
-    def add_sparse(self, key, scenes, n, shape=None):
-        """scenes: per scene (mask, offs, vals) of n elements, arrays or the record's bytes; each checked with check_sparse."""
+    def add_sparse(self, key, scenes, n, shape=None, capacity=None):
+        """scenes: per scene (mask, offs, vals) of n elements, arrays or the record's bytes; each checked with check_sparse.  capacity: None
+        lays the value words out tight (val_base the running total); an int gives every slot that many value words, val_base =
+        arange(N + 1) * capacity, the unused tail of a slot zero -- room for PoolLayout.replace_reference / PoolWriter to put another
+        scene there.  ValueError naming key and scene if a scene holds more."""
         scenes = self._begin(key, scenes)
         planes = []
         for i, s in enumerate(scenes):
@@ -798,9 +806,21 @@ class PoolLayout:
                 planes.append(check_sparse(*s, n, 'stream'))
             except (ValueError, TypeError) as e:
                 raise ValueError(f'PoolLayout[{key!r}] scene {i}: {e}') from None
-        base = np.zeros(len(planes) + 1, np.int64)
-        base[1:] = np.cumsum([p[2].size for p in planes], dtype=np.int64)
-        vals = np.concatenate([p[2] for p in planes]).astype(np.uint32)
+        if capacity is None:
+            base = np.zeros(len(planes) + 1, np.int64)
+            base[1:] = np.cumsum([p[2].size for p in planes], dtype=np.int64)
+            vals = np.concatenate([p[2] for p in planes]).astype(np.uint32)
+        else:
+            capacity = int(capacity)
+            if capacity < 0:
+                raise ValueError(f'PoolLayout[{key!r}]: capacity {capacity}')
+            for i, p in enumerate(planes):
+                if p[2].size > capacity:
+                    raise ValueError(f'PoolLayout[{key!r}] scene {i}: {p[2].size} value words, the slots hold {capacity}')
+            base = np.arange(len(planes) + 1, dtype=np.int64) * capacity
+            vals = np.zeros(len(planes) * capacity, np.uint32)
+            for i, p in enumerate(planes):
+                vals[base[i]:base[i] + p[2].size] = p[2]
         self._end(key, len(planes), int(n), shape, {'kind': 'sparse', 'mask': np.stack([p[0] for p in planes]).astype(np.uint32),
                                        'offs': np.stack([p[1] for p in planes]).astype(np.uint32), 'val_base': base, 'vals': vals})
         return self
@@ -854,7 +874,108 @@ class PoolLayout:
                     self.add_raw(key, rows, dtype, scale, dshape)
             except KeyError as e:
                 raise ValueError(f'PoolLayout[{key!r}]: a scene lacks the record feature {e}') from None
+        self.geometry = (grid, out, test, dict(names))
         return self
+
+    @staticmethod
+    def _empty_plan(N, grid, out, test, names, capacity):
+        """What `empty` builds, without the arrays: [(key, entry, {part: (shape, dtype)})]; a sparse entry carries its 'capacity'."""
+        names = POOL_NAMES if names is None else names
+        capacity = dict(capacity or {})
+        N = int(N)
+        if N < 1:
+            raise ValueError(f'PoolLayout.empty: {N} scenes: an empty pool')
+        plan = []
+        for name, (dtype, shape, crop, scale) in feature_spec(grid, out, test).items():
+            key = names.get(name, name)
+            dshape = decoded_shape(shape, crop)
+            n = int(np.prod(dshape))
+            kind = PACKED_KIND.get(name, 'raw')
+            if kind != 'raw' and n % 32:
+                raise ValueError(f'PoolLayout[{key!r}]: {n} elements per scene, a multiple of 32 only')
+            if n >= 1 << 32:
+                raise ValueError(f'PoolLayout[{key!r}]: {n} elements per scene, fewer than 2^32 only')
+            if kind == 'bits':
+                plan.append((key, {'kind': 'bits', 'n': n, 'shape': dshape}, {'words': ((N, n // 32), np.uint32)}))
+            elif kind == 'sparse':
+                cap = int(capacity.pop(key, n))
+                if cap < 0:
+                    raise ValueError(f'PoolLayout[{key!r}]: capacity {cap}')
+                plan.append((key, {'kind': 'sparse', 'n': n, 'shape': dshape, 'capacity': cap},
+                             {'mask': ((N, n // 32), np.uint32), 'offs': ((N, -(-n // SPARSE_BLOCK) + 1), np.uint32), 'val_base': ((N + 1,), np.int64),
+                              'vals': ((N * cap,), np.uint32)}))
+            else:
+                plan.append((key, {'kind': 'raw', 'n': n, 'shape': dshape, 'dtype': dtype, 'scale': float(scale)},
+                             {'data': ((N, n), np.dtype(_RAW_DTYPE[dtype]))}))
+        if capacity:
+            raise ValueError(f'PoolLayout.empty: capacity names {sorted(capacity)}, which are not sparse keys of the pool')
+        return plan
+
+    @classmethod
+    def empty(cls, N, grid=512, out=256, test=False, names=None, capacity=None):
+        """N all-zero scenes under the standard keys, to be filled by replace_reference (here) or by a PoolWriter (on the device): bits and
+        sparse keys as PACKED_KIND says, the rest raw, as from_examples lays out packed records.  capacity: {key: value words per slot} for the
+        sparse keys; a key that is not named gets n, the dense worst case, which can never reject a scene."""
+        self = cls()
+        for key, entry, parts in cls._empty_plan(N, grid, out, test, names, capacity):
+            arrs = {p: np.zeros(shape, dt) for p, (shape, dt) in parts.items()}
+            if entry['kind'] == 'sparse':
+                arrs['val_base'] = np.arange(int(N) + 1, dtype=np.int64) * entry['capacity']
+            self.entries[key] = dict(entry, **arrs)
+        self.N = int(N)
+        self.geometry = (grid, out, test, dict(POOL_NAMES if names is None else names))
+        return self
+
+    def replace_reference(self, slots, examples, grid=512, out=256, test=False, names=None):
+        """The semantics of PoolWriter.put in NumPy.  examples: parsed, UNPACKED records (parse_example); scene b goes to slot slots[b].
+        It is admitted iff 0 <= slots[b] < N and, for every sparse key, its present words fit the slot: count <= val_base[s + 1] -
+        val_base[s].  An admitted scene replaces EVERY key of its slot -- bits words; mask, scene-relative offs and the present words
+        written from val_base[s] on in element order (the slot's words behind them keep what they held); the raw rows -- and a scene that is
+        not admitted changes no key of any slot.  -> [1 | 0] per scene.  Duplicate slots raise ValueError, and so does a record whose
+        feature has the wrong length or a key whose kind is not the one `empty` gives it."""
+        names = POOL_NAMES if names is None else names
+        slots = [int(s) for s in slots]
+        examples = list(examples)
+        if len(slots) != len(examples):
+            raise ValueError(f'replace_reference: {len(slots)} slots for {len(examples)} scenes')
+        if len(set(slots)) != len(slots):
+            raise ValueError(f'replace_reference: duplicate slots in {slots}')
+        spec = feature_spec(grid, out, test)
+        landed = []
+        for b, (s, ex) in enumerate(zip(slots, examples)):
+            new, fits = {}, 0 <= s < self.N
+            for name, (dtype, shape, crop, scale) in spec.items():
+                key = names.get(name, name)
+                e = self.entries[key]
+                want = PACKED_KIND.get(name, 'raw')
+                try:
+                    a = np.ascontiguousarray(_decoded(ex[name], dtype, shape, crop))
+                except (ValueError, KeyError) as err:
+                    raise ValueError(f'PoolLayout[{key!r}] scene {b}: {err}') from None
+                if e['kind'] != want or e['n'] != a.size or (want == 'raw' and e['dtype'] != dtype):
+                    raise ValueError(f"PoolLayout[{key!r}]: holds {e['kind']} scenes of {e['n']} elements, a replaced scene is {want} of {a.size}")
+                if want == 'bits':
+                    new[key] = (pack_bits(a),)
+                elif want == 'sparse':
+                    new[key] = pack_sparse(a)
+                    if fits and new[key][2].size > int(e['val_base'][s + 1] - e['val_base'][s]):
+                        fits = False
+                else:
+                    new[key] = (a.reshape(-1),)
+            landed.append(int(fits))
+            if not fits:
+                continue
+            for key, parts in new.items():
+                e = self.entries[key]
+                if e['kind'] == 'bits':
+                    e['words'][s] = parts[0]
+                elif e['kind'] == 'sparse':
+                    v0 = int(e['val_base'][s])
+                    e['mask'][s], e['offs'][s] = parts[0], parts[1]
+                    e['vals'][v0:v0 + parts[2].size] = parts[2]
+                else:
+                    e['data'][s] = parts[0]
+        return landed
 
     def check_index(self, idx):
         """A host index list: ValueError unless every index is in [0, N).  -> int64 array."""
@@ -875,7 +996,8 @@ class PoolLayout:
                 if e['kind'] == 'bits':
                     r = unpack_reference('bits', e['words'][s], e['n'])
                 elif e['kind'] == 'sparse':
-                    r = unpack_reference('sparse', e['mask'][s], e['offs'][s], e['vals'][e['val_base'][s]:e['val_base'][s + 1]], e['n'])
+                    v0 = int(e['val_base'][s])                   # a slot may have slack behind its offs[s][-1] value words
+                    r = unpack_reference('sparse', e['mask'][s], e['offs'][s], e['vals'][v0:v0 + int(e['offs'][s][-1])], e['n'])
                 else:
                     a = e['data'][s]
                     a = a.view(np.float32) if e['dtype'] == 'float32' else (a != 0) if e['dtype'] == 'bool' else a
@@ -892,6 +1014,8 @@ class PoolLayout:
     @property
     def nbytes(self):
         """Bytes the pool occupies on the device."""
+        if self.device_only:
+            return sum(int(np.prod(shape)) * np.dtype(dt).itemsize for e in self.entries.values() for shape, dt in e['parts'].values())
         return sum(a.nbytes for key in self.entries for a in self.arrays(key).values())
 
 
@@ -939,8 +1063,11 @@ class ResidentPool:
     The upload goes through pinned staging on the process's one copy stream in pieces of chunk_bytes (HostFeed explains why one large copy
     is wrong while a step is running); an event marks it done and the first gather waits on it.  idx: a device int32 tensor, trusted
     because the kernels clamp it to the pool, or a host list, range-checked (ValueError).
-    Out of scope: a pool is immutable once built.  Replacing scenes in place, or a rolling window over a dataset larger than HBM, is not
-    built; a caller that needs more builds a second pool while the first is in use."""
+    Scenes are replaced in place from the reference's own unpacked records: ResidentPool.empty(N, ...) allocates zero-filled slots (a sparse
+    key's slot holds `capacity` value words), pool.writer(B) returns a PoolWriter whose put(slots, examples) uploads the raw bytes and packs
+    them on the device (stj_pack_bits / stj_pack_sparse_* / stj_pool_put_raw) -- a rolling window over a dataset larger than HBM.
+    Out of scope: replacement from already-packed records (a scatter copy with no packing); a refill overlapped with the running step
+    on a stream of its own (commit runs on the current stream, in front of the gathers); any policy for which slots to evict."""
 
     def __init__(self, layout, device='cuda', chunk_bytes=3 << 19):
         dev = torch.device(device)
@@ -971,6 +1098,42 @@ class ResidentPool:
     @classmethod
     def from_examples(cls, packed_examples, device='cuda', grid=512, out=256, test=False, names=None, chunk_bytes=3 << 19):
         return cls(PoolLayout.from_examples(packed_examples, grid, out, test, names), device, chunk_bytes)
+
+    @classmethod
+    def empty(cls, N, device='cuda', grid=512, out=256, test=False, names=None, capacity=None):
+        """ResidentPool(PoolLayout.empty(...)) without the host copy: the same arrays allocated on the device, zero-filled there (val_base
+        computed there).  pool.layout then describes the keys (kind, n, shape, capacity) and holds no arrays."""
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise RuntimeError('ResidentPool: CUDA (ROCm) device only: the HIP path has no CPU fallback')
+        lay = PoolLayout()
+        lay.device_only, lay.N = True, int(N)
+        lay.geometry = (grid, out, test, dict(POOL_NAMES if names is None else names))
+        self = cls.__new__(cls)
+        self.layout, self.dev, self.N = lay, dev, int(N)
+        self.dev_arrays, self._staging = {}, []
+        for key, entry, parts in PoolLayout._empty_plan(N, grid, out, test, names, capacity):
+            lay.entries[key] = dict(entry, parts=parts)
+            self.dev_arrays[key] = {}
+            for part, (shape, dt) in parts.items():
+                nb = int(np.prod(shape)) * np.dtype(dt).itemsize
+                if part == 'val_base':
+                    d = (torch.arange(int(N) + 1, dtype=torch.int64, device=dev) * entry['capacity']).view(torch.uint8)
+                else:
+                    d = torch.zeros((max(nb, 8),), dtype=torch.uint8, device=dev)          # never empty: a real pointer
+                self.dev_arrays[key][part] = d
+        self.up = torch.cuda.Event()
+        self.up.record(torch.cuda.current_stream(dev))
+        self._ready = False
+        return self
+
+    def _n_vals(self, key):
+        e = self.layout.entries[key]
+        return self.N * e['capacity'] if self.layout.device_only else int(e['val_base'][-1])
+
+    def writer(self, B, chunk_bytes=3 << 19):
+        """A PoolWriter for B scenes per put: every buffer it needs, allocated once."""
+        return PoolWriter(self, B, chunk_bytes)
 
     @property
     def nbytes(self):
@@ -1006,7 +1169,7 @@ class ResidentPool:
         if e['kind'] == 'bits':
             call('stj_gather_bits', _p(d['words']), _p(idx), self.N, _p(dst), B, n, _st())
         elif e['kind'] == 'sparse':
-            call('stj_gather_sparse', _p(d['mask']), _p(d['offs']), _p(d['val_base']), _p(d['vals']), int(e['val_base'][-1]), _p(idx), self.N,
+            call('stj_gather_sparse', _p(d['mask']), _p(d['offs']), _p(d['val_base']), _p(d['vals']), self._n_vals(key), _p(idx), self.N,
                  _p(dst), B, n, _st())
         else:
             call('stj_gather_raw', _p(d['data']), KIND[e['dtype']], _p(idx), self.N, _p(dst), B, n, e['scale'], _st())
@@ -1086,3 +1249,134 @@ class ResidentFeed:
 
     def close(self):
         pass
+
+
+class PoolWriter:
+    """Replaces B scenes of a ResidentPool in place from the reference's own UNPACKED records (parse_example output): the raw bytes go up
+    once and are centre-cropped, bit-packed or stream-compacted on the device, straight into the pool's slots.
+
+        pool = ResidentPool.empty(N, 'cuda', grid, out, test, capacity={'flow': ..., 'gt_flow': ..., 'origin_flow': ...})
+        writer = pool.writer(B)
+        ok = writer.put(slots, examples)         # device int32 [B]: 1 = the scene landed in slots[b], 0 = the pool is unchanged for it
+
+    PoolLayout.replace_reference states the semantics: a scene lands with every key or with none (a slot outside [0, N), or a sparse key
+    whose present words exceed the slot's capacity, rejects it).  Everything is allocated once: pinned staging and the device buffers
+    writer.raw[record name] (uint8 [B, nbytes]), the offs_stage workspace of every sparse key, writer.ok and the persistent writer.slots
+    (device int32 [B]).  put() stages the records through pinned memory on the process's copy stream in pieces of chunk_bytes (HostFeed
+    explains why), lets the current stream wait for them and calls commit().  commit() only launches, on the CURRENT stream -- so it is
+    ordered against that stream's gathers and is capturable in a graph (fill writer.raw[...] and writer.slots between replays): the counts
+    of every sparse key, the admits, then the commit of every key.  It never waits for the device.  slots: a host list is range- and
+    duplicate-checked (ValueError); a device int32 [B] tensor is trusted -- the kernels skip a slot outside the pool and report ok = 0;
+    duplicates in it are the caller's error.  The host arrays of pool.layout, where it has any, are not updated."""
+
+    def __init__(self, pool, B, chunk_bytes=3 << 19):
+        lay = pool.layout
+        if lay.geometry is None:
+            raise ValueError('PoolWriter: a pool laid out by PoolLayout.empty / from_examples (or ResidentPool.empty) only: the keys of a '
+                             'hand-built layout do not say which record feature they hold')
+        grid, out, test, names = lay.geometry
+        self.pool, self.B, self.dev, self.chunk = pool, int(B), pool.dev, max(1, int(chunk_bytes))
+        if self.B < 0:
+            raise ValueError(f'PoolWriter: B {B}')
+        self.features = []                         # (record name, key, entry, nbytes, (T, H, W, C, y0, x0, Ho, Wo))
+        for name, (dtype, shape, crop, scale) in feature_spec(grid, out, test).items():
+            key = names.get(name, name)
+            e = lay.entries.get(key)
+            want = PACKED_KIND.get(name, 'raw')
+            n = int(np.prod(decoded_shape(shape, crop)))
+            if e is None or e['kind'] != want or e['n'] != n or (want == 'raw' and (e['dtype'] != dtype or crop is not None)):
+                raise ValueError(f"PoolWriter: pool key {key!r} is {None if e is None else (e['kind'], e['n'])}, raw records give {want} scenes of "
+                                 f'{n} elements: a pool of packed records (or ResidentPool.empty) only')
+            total = int(np.prod(shape))
+            geom = (1, 1, total, 1, 0, 0, 1, total) if crop is None else (shape[0], shape[1], shape[2], shape[3]) + tuple(crop)
+            self.features.append((name, key, e, total * ITEMSIZE[dtype], geom))
+        rows = max(self.B, 1)                      # never empty: a real pointer, also with B = 0
+        self._host = {f[0]: torch.empty((rows, f[3]), dtype=torch.uint8).pin_memory() for f in self.features}
+        self.raw = {f[0]: torch.zeros((rows, f[3]), dtype=torch.uint8, device=self.dev)[:self.B] for f in self.features}
+        self.offs_stage = {key: torch.zeros((rows, -(-e['n'] // SPARSE_BLOCK) + 1), dtype=torch.int32, device=self.dev)
+                           for _, key, e, _, _ in self.features if e['kind'] == 'sparse'}
+        self.ok = torch.zeros((rows,), dtype=torch.int32, device=self.dev)[:self.B]
+        self.slots = torch.zeros((rows,), dtype=torch.int32, device=self.dev)[:self.B]
+        self.copy = _copy_stream(self.dev)
+        self.up, self.done = torch.cuda.Event(), torch.cuda.Event()
+        self._pending = False                      # an upload from the pinned staging may still be running
+
+    def _set_slots(self, slots):
+        if isinstance(slots, torch.Tensor) and slots.is_cuda:
+            if slots.dtype != torch.int32 or tuple(slots.shape) != (self.B,) or not slots.is_contiguous():
+                raise ValueError(f'PoolWriter: slots must be a contiguous int32 [{self.B}] device tensor, got {slots.dtype} {tuple(slots.shape)}')
+            if slots.data_ptr() != self.slots.data_ptr():
+                self.slots.copy_(slots, non_blocking=True)
+            return
+        host = [int(s) for s in (slots.tolist() if isinstance(slots, torch.Tensor) else slots)]
+        if len(host) != self.B:
+            raise ValueError(f'PoolWriter: {len(host)} slots for a writer of {self.B} scenes')
+        self.pool.layout.check_index(host)
+        if len(set(host)) != len(host):
+            raise ValueError(f'PoolWriter: duplicate slots in {host}')
+        if self.B:
+            self.slots.copy_(torch.tensor(host, dtype=torch.int32))
+
+    def _check_records(self, examples):
+        examples = list(examples)
+        if len(examples) != self.B:
+            raise ValueError(f'PoolWriter: {len(examples)} records for a writer of {self.B} scenes')
+        for name, key, e, nbytes, _ in self.features:
+            for b, ex in enumerate(examples):
+                if name not in ex or len(ex[name]) != nbytes:
+                    raise ValueError(f"PoolWriter: feature {name} of scene {b}: {len(ex[name]) if name in ex else 'no'} bytes, expected {nbytes}")
+        return examples
+
+    def put(self, slots, examples):
+        """examples: B parsed unpacked records ({feature: bytes}); scene b replaces pool slot slots[b].  -> writer.ok."""
+        examples = self._check_records(examples)
+        self._set_slots(slots)
+        self.stage(examples)
+        return self.commit()
+
+    def stage(self, examples):
+        """The upload half of put(): the records' bytes into writer.raw through pinned memory on the copy stream; the current stream waits
+        for them (a device-side wait), so a commit() issued next on it packs these records."""
+        examples = self._check_records(examples)
+        if self._pending:
+            self.up.synchronize()                  # the previous upload has left the pinned staging (a host wait on the copy alone)
+        for name, _, _, nbytes, _ in self.features:
+            h = self._host[name].numpy()
+            for b, ex in enumerate(examples):
+                h[b] = np.frombuffer(ex[name], np.uint8)
+        main = torch.cuda.current_stream(self.dev)
+        self.done.record(main)                     # whatever read writer.raw before (the previous commit) is in front of this
+        with torch.cuda.stream(self.copy):
+            self.copy.wait_event(self.done)
+            for name, _, _, nbytes, _ in self.features:
+                hs, ds = self._host[name].view(-1), self.raw[name].view(-1)
+                for i in range(0, ds.numel(), self.chunk):
+                    ds[i:i + self.chunk].copy_(hs[i:i + self.chunk], non_blocking=True)
+            self.up.record(self.copy)
+        self._pending = True
+        main.wait_event(self.up)
+
+    def commit(self, slots=None):
+        """Packs what writer.raw holds into the slots writer.slots names (slots: copied there first).  Launches only, on the current stream."""
+        if slots is not None:
+            self._set_slots(slots)
+        self.pool._await_upload()
+        B, N, st = self.B, self.pool.N, _st()
+        ok, sl, arrs = _p(self.ok), _p(self.slots), self.pool.dev_arrays
+        sparse = [f for f in self.features if f[2]['kind'] == 'sparse']
+        for name, key, e, _, geom in sparse:
+            call('stj_pack_sparse_count', _p(self.raw[name]), _p(self.offs_stage[key]), B, *geom, st)
+        for i, (name, key, e, _, geom) in enumerate(sparse):
+            call('stj_pool_admit', _p(self.offs_stage[key]), -(-e['n'] // SPARSE_BLOCK), _p(arrs[key]['val_base']), sl, N, ok, B, int(i == 0), st)
+        if not sparse:
+            call('stj_pool_admit', None, 0, None, sl, N, ok, B, 1, st)                      # the range check of the slots alone
+        for name, key, e, _, geom in self.features:
+            d = arrs[key]
+            if e['kind'] == 'bits':
+                call('stj_pack_bits', _p(self.raw[name]), ok, sl, N, _p(d['words']), B, *geom, st)
+            elif e['kind'] == 'sparse':
+                call('stj_pack_sparse_commit', _p(self.raw[name]), _p(self.offs_stage[key]), ok, sl, N, _p(d['mask']), _p(d['offs']),
+                     _p(d['val_base']), _p(d['vals']), self.pool._n_vals(key), B, *geom, st)
+            else:
+                call('stj_pool_put_raw', _p(self.raw[name]), ITEMSIZE[e['dtype']], ok, sl, N, _p(d['data']), B, e['n'], st)
+        return self.ok

@@ -7,7 +7,9 @@
 Feed modes, all on the SAME captured graph in one process: `resident` (inputs stay in HBM, no feed), `f32` (HostFeed, decoded float32
 tensors), `raw` (HostFeed, the record's own bytes: bool grids and the int8 map one byte per element, float32 flows), `packed`
 (PackedFeed: bool grids one bit per element, flows as mask + non-zero words, int8 map), `pool` (ResidentFeed, DESIGN 4u: --pool-scenes x B
-blob scenes packed the same way stay in HBM, every step gathers a freshly sampled batch by device index, nothing is uploaded).  Per visit
+blob scenes packed the same way stay in HBM, every step gathers a freshly sampled batch by device index, nothing is uploaded), `replace`
+(opt-in through --modes: the same pool built by ResidentPool.empty and filled by a PoolWriter from raw records; every
+--replace-every steps one put() of B raw records replaces B slots in front of the landing).  Per visit
 every mode is timed TWICE in a row,
 the modes alternating, --pairs visits: the spread of repeated runs of one mode is measured in the same call.  One JSON line per run:
 scenes/s, bytes uploaded per scene, the density of the synthetic scene.
@@ -15,6 +17,10 @@ scenes/s, bytes uploaded per scene, the density of the synthetic scene.
   --all            runs both configs as child processes, each under its own `timeout`; --out FILE collects their lines
   --trace          a few PackedFeed and ResidentFeed landings at the config's shapes and nothing else (no model): the workload of a
                    `rocprofv3 --kernel-trace --stats` run; prints the bytes each unpack / gather kernel reads and writes per landing
+  --trace-replace  the same for the writer: 10 commits of B raw records and 10 gathers of the slots they went to, no model
+  --replace-put    what one PoolWriter.put of B raw records costs at --put-grid / --put-out (default the real 512 / 256 geometry), no model:
+                   host copy into pinned staging, H2D alone (events on the copy stream), commit alone (events on the main stream), the
+                   whole put (host clock to a device synchronise), and the host's pack_example over the same records
 
 The scenes are synthetic: --blobs rectangular vehicles per scene on a zero background, occupancy in every time step, flow non-zero only
 inside them (random-normal flow would be dense, and `sparse` then larger than raw).  Real Waymo densities are not available here.
@@ -41,6 +47,12 @@ ap.add_argument('--seed', type=int, default=1234)
 ap.add_argument('--pool-scenes', type=int, default=8, help='mode pool: the pool holds this many batches of scenes')
 ap.add_argument('--all', action='store_true')
 ap.add_argument('--trace', action='store_true')
+ap.add_argument('--trace-replace', action='store_true')
+ap.add_argument('--replace-put', action='store_true')
+ap.add_argument('--replace-every', type=int, default=8, help='mode replace: one put of B records every this many steps')
+ap.add_argument('--put-grid', type=int, default=512)
+ap.add_argument('--put-out', type=int, default=256)
+ap.add_argument('--put-reps', type=int, default=10)
 ap.add_argument('--timeout', type=int, default=420, help='--all: seconds per child')
 ap.add_argument('--out', default=None, help='append the JSON lines to this file as well')
 a = ap.parse_args()
@@ -59,7 +71,7 @@ if a.all:
     for cfg in ('train', 'infer'):
         cmd = ['timeout', '-k', '10', str(a.timeout), sys.executable, os.path.abspath(__file__), '--config', cfg, '--modes', a.modes,
                '--steps', str(a.steps), '--warmup', str(a.warmup), '--pairs', str(a.pairs), '--blobs', str(a.blobs), '--seed', str(a.seed),
-               '--pool-scenes', str(a.pool_scenes)]
+               '--pool-scenes', str(a.pool_scenes), '--replace-every', str(a.replace_every)]
         if a.out:
             cmd += ['--out', a.out]
         r = subprocess.run(cmd)
@@ -72,8 +84,8 @@ import numpy as np
 import torch
 
 import bench
-from strajnet_amd.data import (HostFeed, PackedFeed, PoolLayout, ResidentFeed, ResidentPool, SparseHost, bits_host, pack_bits,
-                               pack_sparse)
+from strajnet_amd.data import (POOL_NAMES, HostFeed, PackedFeed, PoolLayout, ResidentFeed, ResidentPool, SparseHost, bits_host,
+                               feature_spec, pack_bits, pack_example, pack_sparse)
 
 assert torch.cuda.is_available(), 'bench_feed.py needs a GPU'
 dev = torch.device('cuda', 0)
@@ -187,8 +199,154 @@ def pool_bytes(feed):
     return per
 
 
+def blob_records(B, seed, blobs, grid=256, out=256):
+    """B raw records ({feature: bytes}, as parse_example gives them for the reference's own files) of blob scenes at (grid, out): the
+    ground truth at the full grid, centre-cropped to `out` by whoever decodes it."""
+    x = blob_scenes(B, seed, blobs, grid, grid)
+    as_bytes = {'bool': lambda v: (v != 0).to(torch.uint8), 'int8': lambda v: torch.round(v * 256.0).to(torch.int8),
+                'float32': lambda v: v.float(), 'float64': lambda v: v.double()}
+    recs = []
+    for b in range(B):
+        rec = {}
+        for name, (dtype, shape, crop, scale) in feature_spec(grid, out).items():
+            v = as_bytes[dtype](x[POOL_NAMES[name]][b]).contiguous().numpy()
+            assert v.shape == tuple(shape), (name, v.shape, shape)
+            rec[name] = v.tobytes()
+        recs.append(rec)
+    return recs
+
+
+def record_capacity(batches, grid, out):
+    """{key: value words per slot}: the largest present-word count of any sparse feature over the records, rounded up to 1024."""
+    spec = feature_spec(grid, out)
+    cap = {}
+    for name in ('vec_flow', 'gt_flow', 'origin_flow'):
+        dtype, shape, crop, _ = spec[name]
+        most = 0
+        for recs in batches:
+            for r in recs:
+                v = np.frombuffer(r[name], '<u4').reshape(shape)
+                if crop is not None:
+                    v = v[:, crop[0]:crop[0] + crop[2], crop[1]:crop[1] + crop[3]]
+                most = max(most, int(np.count_nonzero(v)))
+        cap[POOL_NAMES[name]] = -(-max(most, 1) // 1024) * 1024
+    return cap
+
+
+class ReplaceFeed(ResidentFeed):
+    """ResidentFeed over a pool that a PoolWriter refills: every `every` landings one put() of B raw records replaces B slots (walking
+    round the pool) in front of the gathers, on the same stream."""
+
+    def __init__(self, static, pool, sampler, batches, every):
+        super().__init__(static, pool, sampler)
+        self.writer, self.batches, self.every, self.count, self.puts = pool.writer(self.B), batches, max(1, every), 0, 0
+
+    def land(self, idx=None):
+        if self.count % self.every == 0:
+            first = (self.puts * self.B) % self.pool.N
+            self.writer.put(list(range(first, first + self.B)), self.batches[self.puts % len(self.batches)])
+            self.puts += 1
+        self.count += 1
+        super().land(idx)
+
+
+def make_replace_feed(static):
+    """-> (ReplaceFeed over ResidentPool.empty of --pool-scenes x B slots, every slot filled by the writer; raw bytes uploaded per batch,
+    averaged over --replace-every steps)."""
+    batches = [blob_records(B, a.seed + 1 + j, a.blobs) for j in range(a.pool_scenes)]
+    pool = ResidentPool.empty(a.pool_scenes * B, dev, 256, 256, capacity=record_capacity(batches, 256, 256))
+    feed = ReplaceFeed(static, pool, pool.sampler(B, seed=a.seed), batches, a.replace_every)
+    for j, recs in enumerate(batches):
+        ok = feed.writer.put(list(range(j * B, (j + 1) * B)), recs)
+        assert ok.cpu().tolist() == [1] * B
+    return feed, sum(len(v) for v in batches[0][0].values()) * B / feed.every
+
+
+def writer_bytes(writer):
+    """Per key: the kernels of one commit and the bytes they read and write (the source is read twice for a sparse key: count + commit)."""
+    per = {}
+    nb = writer.B
+    for name, key, e, nbytes, geom in writer.features:
+        n = e['n']
+        if e['kind'] == 'bits':
+            per[key] = {'kernel': 'pack_bits_kernel', 'read_bytes': nb * n, 'written_bytes': nb * n // 8}
+        elif e['kind'] == 'sparse':
+            stage = writer.offs_stage[key].cpu().numpy().view(np.uint32)
+            present = int(stage[:, -1].sum())
+            per[key] = {'kernel': 'pack_count_kernel + pack_commit_kernel', 'count_read_bytes': nb * n * 4,
+                        'commit_read_bytes': nb * n * 4, 'commit_written_bytes': nb * (n // 8 + 4 * stage.shape[1]) + 4 * present}
+        else:
+            per[key] = {'kernel': 'put_raw_kernel', 'read_bytes': nb * nbytes, 'written_bytes': nb * nbytes}
+    return per
+
+
+if a.replace_put:
+    grid, out, reps = a.put_grid, a.put_out, a.put_reps
+    batches = [blob_records(B, a.seed + j, a.blobs, grid, out) for j in range(2)]
+    raw_bytes = sum(len(v) for v in batches[0][0].values())
+    t0 = time.perf_counter()
+    packed = [pack_example(r, grid, out) for r in batches[0]]
+    t_pack = time.perf_counter() - t0
+    pool = ResidentPool.empty(2 * B, dev, grid, out, capacity=record_capacity(batches, grid, out))
+    w = pool.writer(B)
+    slots = [list(range(B)), list(range(B, 2 * B))]
+    for j in range(2):                                                   # warm-up: code objects, pinned pages
+        assert w.put(slots[j], batches[j]).cpu().tolist() == [1] * B
+    torch.cuda.synchronize()
+    main = torch.cuda.current_stream(dev)
+    t_put, t_stage_host, t_h2d, t_commit = [], [], [], []
+    for r in range(reps):
+        t0 = time.perf_counter()
+        w._set_slots(slots[r % 2])
+        w.stage(batches[r % 2])
+        t1 = time.perf_counter()
+        w.commit()
+        torch.cuda.synchronize()
+        t_put.append(time.perf_counter() - t0)
+        t_stage_host.append(t1 - t0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(w.copy):                                  # the H2D copies of stage() again, without its host-side fill
+            e0.record(w.copy)
+            for name in w.raw:
+                hs, ds = w._host[name].view(-1), w.raw[name].view(-1)
+                for i in range(0, ds.numel(), w.chunk):
+                    ds[i:i + w.chunk].copy_(hs[i:i + w.chunk], non_blocking=True)
+            e1.record(w.copy)
+        torch.cuda.synchronize()
+        t_h2d.append(e0.elapsed_time(e1) * 1e-3)
+        c0, c1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        c0.record(main)
+        w.commit()
+        c1.record(main)
+        torch.cuda.synchronize()
+        t_commit.append(c0.elapsed_time(c1) * 1e-3)
+    ms = lambda v: {'mean': round(1e3 * float(np.mean(v)), 3), 'min': round(1e3 * min(v), 3), 'max': round(1e3 * max(v), 3)}
+    emit({'mode': 'replace-put', 'grid': grid, 'out': out, 'batch': B, 'reps': reps, 'blobs': a.blobs, 'raw_bytes_per_scene': raw_bytes,
+          'pool_bytes_per_scene': round(pool.nbytes / pool.N), 'put_ms': ms(t_put), 'stage_host_ms': ms(t_stage_host), 'h2d_ms': ms(t_h2d),
+          'h2d_GBps': round(raw_bytes * B / float(np.mean(t_h2d)) / 1e9, 2), 'commit_ms': ms(t_commit),
+          'host_pack_example_ms': round(1e3 * t_pack, 1), 'launches_per_commit': 2 * 3 + 10})
+    sys.exit(0)
+
+if a.trace_replace:
+    batches = [blob_records(B, a.seed + j, a.blobs) for j in range(2)]
+    pool = ResidentPool.empty(2 * B, dev, 256, 256, capacity=record_capacity(batches, 256, 256))
+    pool.wait()
+    w = pool.writer(B)
+    static = {k: torch.zeros((B,) + e['shape'], device=dev) for k, e in pool.layout.entries.items()}
+    for j in range(2):
+        assert w.put(list(range(j * B, (j + 1) * B)), batches[j]).cpu().tolist() == [1] * B
+    for _ in range(10):
+        w.commit()
+    idx = torch.arange(B, 2 * B, dtype=torch.int32, device=dev)
+    for _ in range(10):
+        pool.gather_into(static, idx)
+    torch.cuda.synchronize()
+    emit({'mode': 'trace', 'feed': 'replace', 'config': 'train', 'batch': B, 'commits': 12, 'gathers': 10, 'blobs': a.blobs,
+          'pool_scenes': pool.N, 'pool_bytes_per_scene': pool.nbytes / pool.N, 'per_commit': writer_bytes(w)})
+    sys.exit(0)
+
 xh = blob_scenes(B, a.seed, a.blobs)
-density = {k: round(float((xh[k] != 0).float().mean()), 5) for k in BITS + SPARSE}
+density ={k: round(float((xh[k] != 0).float().mean()), 5) for k in BITS + SPARSE}
 
 if a.trace:
     keys = ('ogm', 'map_img', 'obs', 'occ', 'flow') if a.config == 'infer' else tuple(xh)
@@ -254,7 +412,8 @@ def timed(feed):
 modes = a.modes.split(',')
 feeds = {}
 for m in modes:
-    feeds[m] = (None, 0) if m == 'resident' else make_pool_feed(graphed.static) if m == 'pool' else make_feed(m, graphed.static, xh)
+    feeds[m] = ((None, 0) if m == 'resident' else make_pool_feed(graphed.static) if m == 'pool' else make_replace_feed(graphed.static)
+                if m == 'replace' else make_feed(m, graphed.static, xh))
     if feeds[m][0] is not None:
         feeds[m][0].start()
 for visit in range(a.pairs):
@@ -265,7 +424,8 @@ for visit in range(a.pairs):
             emit({'config': a.config, 'mode': m, 'visit': visit, 'rep': rep, 'batch': B, 'steps': a.steps, 'warmup': a.warmup,
                   'scenes_per_s': round(B * a.steps / dt, 1), 'ms_per_step': round(dt / a.steps * 1e3, 4),
                   'upload_bytes_per_scene': round(nbytes / B), 'blobs': a.blobs, 'density': density,
-                  **({'pool_scenes': feed.pool.N, 'pool_bytes_per_scene': round(feed.pool.nbytes / feed.pool.N)} if m == 'pool' else {})})
+                  **({'pool_scenes': feed.pool.N, 'pool_bytes_per_scene': round(feed.pool.nbytes / feed.pool.N)} if m in ('pool', 'replace') else {}),
+                  **({'replace_every': feed.every, 'puts': feed.puts} if m == 'replace' else {})})
 for feed, _ in feeds.values():
     if feed is not None:
         feed.wait_uploaded()
