@@ -406,7 +406,18 @@ int stj_upconv_dgrad(const void* dP, const void* Wd, void* dX, const void* Xelu,
 int stj_upconv_wgrad(const void* X, const void* dP, float* dWeff, float* dbias, int db_parts, int F, int Hi, int Wi, int Cin,
                      int Cout, int wg_budget, int dtype, hipStream_t stream);
 /* wgrad: dbias (optional) is f32 [db_parts][Cout], "+=": workgroup i adds its share of the bias gradient into copy i % db_parts
- * and the caller sums the copies (db_parts = 1: plain [Cout]). */
+ * and the caller sums the copies (db_parts = 1: plain [Cout]).
+ * What tests/test_upconv_wgrad_abi_gpu.py pins down: Cin and Cout are multiples of 8 in the 16-bit types and of 4 in f32, F, Hi and Wi
+ * positive, db_parts >= 1 with a dbias, 0 <= wg_budget <= 4096 (STJ_EINVAL otherwise, nothing launched).  X and dP are 16-byte aligned
+ * (rows are read as 16-byte pieces; not checked) and are only read, and never outside their own extents.  dWeff is ACCUMULATED, like dbias:
+ * the kernels add with f32 atomics to whatever the buffers hold (the caller zeroes dWeff because the fold adds all of it to dW).  The copies
+ * of dbias are contiguous, copy i at dbias + i * Cout, and are selected by workgroup index (512-thread kernel: by 2 * index + column
+ * parity), so which copy holds what depends on the launch geometry and only the sum over the copies is defined.
+ * Kernels: bf16 with Wi % 32 == 0 and Hi % 4 == 0 (128-pixel chunks of 4 rows x 32 columns), or else Wi % 16 == 0 and Hi % 8 == 0 (8 rows x
+ * 16 columns), takes the transpose-read kernels: the 512-thread one when there are at least 2048 chunks and Hi % 8 == 0 (Hi % 16 == 0 for
+ * the 16-column chunks), the 256-thread one below; channel tile 48 x 96 for Cout <= 48 and Cin <= 96, all 96 couts x 64 cins for Cout == 96
+ * and Cin % 64 == 0 (512-thread kernel only), 64 x 64 otherwise.  Every other shape, f32 and fp16 take the generic kernel (row segments of
+ * 32 columns, any Hi and Wi) with the 48 x 96 or the 64 x 64 channel tile.  wg_budget is read by the 512-thread kernel alone. */
 /* Output heads: Conv2D 3x3 SAME C->2, no activation (modules.py:767-770), written with strides straight into the
  * [B,H,W,32] f32 model output (concat + transpose of modules.py:770,838).  Y element (b,t,y,x,o) at
  * Y + b*y_bstride + t*y_tstride + (y*W+x)*y_pstride + o.  bwd with elu_in != 0: X is an ELU output, dX is multiplied by

@@ -2,6 +2,8 @@
 
 Tolerances: f32 mode (exact-f32 MFMA, the parity mode) ~1e-4 relative-to-scale; bf16 mode ~3e-2; fp16 mode ~5e-3.
 All calls go through the C-ABI library via strajnet_amd.ops.
+The up-conv weight gradient (stj_upconv_prep / _wgrad / _fold) is held per dispatch path, in exact integers and per element against float64,
+by test_upconv_wgrad_abi_gpu.py; the test_upconv cases here reach its generic and 256-thread kernels only.
 """
 import math
 

@@ -21,6 +21,8 @@ percent -- a dropped tap, a halo column read twice, one tile's flush lost -- fai
     weight / bias gradients: exact bf16 operands, f32 accumulation, so only the summation order differs: measured 1e-9 .. 2e-8,
                            gate 2^-22 (2.4e-7); where the 16-bit run rounds dpre (ELU layers, output heads) 3.2e-5 / 8.4e-6, gate 2x
 Reference semantics: /root/reference modules.py:746-770 (decoder), :40-46,103-134 (Swin dense layers).
+The up-conv weight gradient at the shapes that take the 512-thread upconv_wgrad_tr4_kernel (2048 chunks and more; the largest shape here has
+1024), against float64 instead of the f32 HIP path: test_upconv_wgrad_abi_gpu.py.
 """
 import os
 
