@@ -455,9 +455,15 @@ int stj_outconv_pair_gather_q(const void* Z0, const void* Z1, const float* bias0
  * strajnet_amd/submission.py.  out: the streams back to back in the order scene, waypoint, (obs, occ, flow); offsets uint32 [B*Tn*3 + 1]:
  * stream s is out[offsets[s] .. offsets[s + 1]).  stj_compress_sizes: the bytes of the caller-owned scratch `work` (not zeroed) and the
  * capacity `out` must have (n + 5 ceil(n / 8192) + 6 per plane of n bytes).  Tn = 8, H * W a multiple of 256, 16-byte aligned buffers,
- * less than 4 GiB of capacity; STJ_EUNSUPPORTED otherwise.  No host synchronisation, no allocation: three launches on `stream`. */
+ * less than 4 GiB of capacity; STJ_EUNSUPPORTED otherwise.  No host synchronisation, no allocation: three launches on `stream`.
+ * stj_compress_waypoints_level: level 1 is stj_compress_waypoints, launch for launch; level 2 writes every segment in the shortest of
+ * three forms -- stored, the fixed code, or a dynamic Huffman code (BTYPE 10) built for that segment over the same tokens
+ * (compress_reference(level=2) states it) -- with another encode kernel in front of the same two; same sizes, workspace and shape
+ * limits, never a longer stream than level 1's.  Any other level: STJ_EINVAL. */
 int stj_compress_sizes(int B, int Tn, int H, int W, long long* work_bytes, long long* out_capacity);
 int stj_compress_waypoints(const uint8_t* Q, void* work, uint8_t* out, uint32_t* offsets, int B, int Tn, int H, int W, hipStream_t stream);
+int stj_compress_waypoints_level(const uint8_t* Q, void* work, uint8_t* out, uint32_t* offsets, int B, int Tn, int H, int W, int level,
+                                 hipStream_t stream);
 int stj_outconv_bwd(const void* X, const float* W, const float* dY, void* dX, float* dW, float* db, int F, int Hh, int Ww,
                     int C, int Tn, long long y_bstride, long long y_tstride, long long y_pstride, int elu_in, void* ws,
                     long long ws_bytes, int dtype, hipStream_t stream);

@@ -30,17 +30,21 @@ DF_HD uint32_t df_literal(uint32_t v, int* nbits) {
   return df_rev32(0x190u + v - 144u) >> 23;
 }
 
+// length code 257..285 of a match of length m (3..258): *eb its count of extra bits, *ex their value
+DF_HD uint32_t df_len_code(int m, uint32_t* eb, uint32_t* ex) {
+  const uint32_t l = (uint32_t)(m - 3);
+  *eb = 0; *ex = 0;
+  if (m == 258) return 285;
+  if (l < 8) return 257 + l;
+  *eb = (uint32_t)(31 - __builtin_clz(l)) - 2;            // lengths 11.. come in groups of 4 codes per count of extra bits
+  *ex = l & ((1u << *eb) - 1);
+  return 261 + 4 * *eb + ((l >> *eb) & 3);
+}
+
 // a match of length m (3..258) at distance d (1 or 2): length code 257..285 + its extra bits + the 5-bit distance code d - 1
 DF_HD uint32_t df_match(int m, int d, int* nbits) {
-  const uint32_t l = (uint32_t)(m - 3);
-  uint32_t sym, eb = 0, ex = 0;
-  if (m == 258) sym = 285;
-  else if (l < 8) sym = 257 + l;
-  else {
-    eb = (uint32_t)(31 - __builtin_clz(l)) - 2;           // lengths 11.. come in groups of 4 codes per count of extra bits
-    sym = 261 + 4 * eb + ((l >> eb) & 3);
-    ex = l & ((1u << eb) - 1);
-  }
+  uint32_t eb, ex;
+  const uint32_t sym = df_len_code(m, &eb, &ex);
   uint32_t hv; int hn;
   if (sym < 280) { hv = df_rev32(sym - 256) >> 25; hn = 7; }
   else { hv = df_rev32(0xC0u + sym - 280) >> 24; hn = 8; }
@@ -61,20 +65,29 @@ DF_HD uint32_t df_match_mask(const uint32_t* w, uint32_t prev, int d) {
   return mask;
 }
 
-// The token that byte `e` of a thread's run contributes (*nbits = 0: none, the byte is covered by a match that starts earlier).
+// The role of byte `e` of a thread's run: -1 a literal, 0 none (the byte is covered by a match that starts earlier), else the length
+// of the match that starts with it.
 // nm: the run's NON-matchable flags (bytes past the segment's end count as non-matchable); base: the run's first index in the segment;
 // P: index of the last non-matchable byte in front of the run (-1: none); N: index of the first one behind it (DF_SEG: none).
 // The stretch of matchable bytes around the byte is [st, en): matches of 258 start every 258 bytes from st while at least 3 bytes are
 // left; the last one takes all that is left if that is at least 3, else those bytes are literals.
-DF_HD uint32_t df_token(uint32_t nm, int e, int base, int P, int N, uint32_t byte, int d, int* nbits) {
-  if ((nm >> e) & 1) return df_literal(byte, nbits);
+DF_HD int df_role(uint32_t nm, int e, int base, int P, int N) {
+  if ((nm >> e) & 1) return -1;
   const uint32_t lo = nm & ((1u << e) - 1u);
   const uint32_t hi = e == 31 ? 0u : nm >> (e + 1);
   const int st = lo ? base + 32 - __builtin_clz(lo) : P + 1;
   const int en = hi ? base + e + 1 + __builtin_ctz(hi) : N;
   const int o = base + e - st;
   const int rem = (en - st) - (o / 258) * 258;
-  if (rem < 3) return df_literal(byte, nbits);
-  if (o % 258) { *nbits = 0; return 0; }
-  return df_match(rem < 258 ? rem : 258, d, nbits);
+  if (rem < 3) return -1;
+  if (o % 258) return 0;
+  return rem < 258 ? rem : 258;
+}
+
+// The token that byte `e` contributes in the fixed Huffman code (*nbits = 0: none).
+DF_HD uint32_t df_token(uint32_t nm, int e, int base, int P, int N, uint32_t byte, int d, int* nbits) {
+  const int r = df_role(nm, e, base, P, N);
+  if (r < 0) return df_literal(byte, nbits);
+  if (r == 0) { *nbits = 0; return 0; }
+  return df_match(r, d, nbits);
 }

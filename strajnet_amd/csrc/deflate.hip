@@ -5,6 +5,8 @@
 //
 //   deflate_encode_kernel   one workgroup per (plane, segment of DF_SEG bytes): the segment's DEFLATE block(s) into its slot of the
 //                           workspace, its byte count and its Adler-32 partials into the segment table
+//   deflate_encode_dyn_kernel  level 2: the same workgroup, slot and table entry; the segment's block in the shortest of its stored,
+//                           fixed and dynamic-Huffman forms (the code is built per segment; the per-symbol rules: deflate_dyn.h)
 //   deflate_offsets_kernel  one workgroup: per plane the scan of its segments' byte counts and its Adler-32, the scan of the planes'
 //                           totals -> `offsets`, and every stream's header and trailer
 //   deflate_pack_kernel     one workgroup per (plane, segment): the slot's bytes to their place in the packed buffer
@@ -14,6 +16,7 @@
 // scene, waypoint, (obs, occ, flow).
 #include "common.h"
 #include "deflate.h"
+#include "deflate_dyn.h"
 
 static_assert(DF_SEG >= 4096 && DF_SEG <= 16384 && (DF_SEG & (DF_SEG - 1)) == 0, "DF_SEG: a power of two, 64 KB of static LDS at most");
 constexpr int DF_NW = DF_NT / 64;          // waves per workgroup
@@ -180,6 +183,268 @@ __global__ __launch_bounds__(DF_NT) void deflate_encode_kernel(const uint8_t* __
   }
 }
 
+// ---------------------------------------------------------------------------------------------------- level 2
+// The arrays of one code construction, in LDS.
+struct DfdWork { uint32_t* srt; uint32_t* iw; uint16_t* lpar; uint16_t* ipar; uint16_t* idep; int* lc; int* nx; int* nused; };
+
+// huffman_code_lengths + the canonical codes over cnt[0 .. NSYM) by the whole workgroup: the rank sort, the leaves' depths, the lengths
+// and the codes one symbol per thread; the merge, the internal depths and the Kraft repair on one lane.  cnt is complete and visible on
+// entry; len and code are on return.
+template <int NSYM, int LIMIT>
+__device__ __forceinline__ void dfd_build(const uint32_t* cnt, uint8_t* len, uint16_t* code, const DfdWork& k, int tid) {
+  if (tid <= LIMIT) k.lc[tid] = 0;
+  if (tid == 0) *k.nused = 0;
+  __syncthreads();
+  for (int s = tid; s < NSYM; s += DF_NT) {
+    len[s] = 0;
+    if (cnt[s]) { k.srt[dfd_rank(cnt, NSYM, s)] = dfd_key(cnt[s], s); atomicAdd(k.nused, 1); }
+  }
+  __syncthreads();
+  const int n = *k.nused;
+  if (tid == 0 && n >= 2) { dfd_merge(k.srt, n, k.iw, k.lpar, k.ipar); dfd_depths(k.ipar, n, k.idep); }
+  __syncthreads();
+  if (n >= 2) {
+    for (int i = tid; i < n; i += DF_NT) atomicAdd(&k.lc[dfd_leaf_len(k.lpar, k.idep, i, LIMIT)], 1);
+  } else if (n == 1 && tid == 0) k.lc[1] = 1;
+  __syncthreads();
+  if (tid == 0) { dfd_kraft(k.lc, LIMIT); dfd_next_codes(k.lc, LIMIT, k.nx); }
+  __syncthreads();
+  for (int i = tid; i < n; i += DF_NT) len[k.srt[i] & 511u] = (uint8_t)dfd_len_of_rank(k.lc, LIMIT, n, i);
+  __syncthreads();
+  for (int s = tid; s < NSYM; s += DF_NT) code[s] = len[s] ? (uint16_t)dfd_code(len, k.nx, s) : (uint16_t)0;
+  __syncthreads();
+}
+
+// Bits laid end to end from bit `at` of bb: accumulated in a register, a whole word at a time into the zeroed buffer by OR.
+struct DfdSink {
+  uint32_t* bb; int wi, fill; unsigned long long acc;
+  __device__ __forceinline__ DfdSink(uint32_t* b, int at) : bb(b), wi(at >> 5), fill(at & 31), acc(0) {}
+  __device__ __forceinline__ void put(uint32_t v, int nb) {                      // nb <= 25
+    acc |= (unsigned long long)v << fill;
+    fill += nb;
+    if (fill >= 32) { atomicOr(&bb[wi], (uint32_t)acc); acc >>= 32; fill -= 32; ++wi; }
+  }
+  __device__ __forceinline__ void flush() { if (fill > 0 && acc) atomicOr(&bb[wi], (uint32_t)acc); }
+};
+
+__global__ __launch_bounds__(DF_NT) void deflate_encode_dyn_kernel(const uint8_t* __restrict__ Q, uint8_t* __restrict__ slots, uint32_t* __restrict__ table,
+                                                                   int HW, int nso, int nsf) {
+  __shared__ __attribute__((aligned(16))) uint32_t inw[4 + DF_SEG / 4];         // 16 bytes of history, then the segment
+  __shared__ __attribute__((aligned(16))) uint32_t bb[DF_SLOT / 4 + 4];         // the segment's output, built by OR into zeroed words
+  __shared__ int sc[6][DF_NW];
+  __shared__ uint32_t hist[DFD_NSEQ], srt[DFD_NSEQ], iw[DFD_NSEQ], cc[DFD_NCL]; // counts per literal/length and per code-length symbol
+  __shared__ uint16_t lpar[DFD_NSEQ], ipar[DFD_NSEQ], idep[DFD_NSEQ], lcode[DFD_NSEQ], ccode[32];
+  __shared__ uint8_t ll[DFD_NSEQ], cl[32], rsym[DFD_NSEQ], rext[DFD_NSEQ];
+  __shared__ int lc[16], nx[16], meta[3];                                        // meta: used symbols, literal/length codes, RLE symbols
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const DfSeg s = df_locate(blockIdx.x, HW, nso, nsf);
+  const int len = s.len, d = s.d;
+  const uint4* src4 = reinterpret_cast<const uint4*>(Q + s.src);
+  uint4* in4 = reinterpret_cast<uint4*>(inw);
+  for (int v = tid; v < len / 16; v += DF_NT) in4[1 + v] = src4[v];
+  if (tid == 0) in4[0] = s.seg ? src4[-1] : make_uint4(0, 0, 0, 0);               // history: the same plane's previous segment only
+  for (int i = tid; i < DFD_NSEQ; i += DF_NT) hist[i] = i == 256 ? 1u : 0u;       // EOB once
+  __syncthreads();
+
+  // this thread's run of 32 bytes, its matchable flags, P and N: as in deflate_encode_kernel
+  const int base = tid * DF_RUN, cnt = max(0, min(DF_RUN, len - base));
+  uint32_t w[8];
+  {
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    const uint4 a = cnt > 0 ? in4[1 + 2 * tid] : z, b = cnt > 16 ? in4[2 + 2 * tid] : z;
+    w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w; w[4] = b.x; w[5] = b.y; w[6] = b.z; w[7] = b.w;
+  }
+  uint32_t mask = cnt > 0 ? df_match_mask(w, inw[3 + 8 * tid], d) : 0u;
+  mask &= cnt == DF_RUN ? ~0u : (1u << cnt) - 1u;
+  if (s.seg == 0 && tid == 0) mask &= ~((1u << d) - 1u);                           // no history in front of the plane
+  const uint32_t nm = ~mask;
+  int P, N;
+  {
+    int a = nm ? base + 31 - __builtin_clz(nm) : -1, b = nm ? base + __builtin_ctz(nm) : DF_SEG;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int ya = __shfl_up(a, o), yb = __shfl_down(b, o);
+      if (lane >= o) a = max(a, ya);
+      if (lane + o < 64) b = min(b, yb);
+    }
+    if (lane == 63) sc[0][wv] = a;
+    if (lane == 0) sc[1][wv] = b;
+    P = __shfl_up(a, 1); N = __shfl_down(b, 1);
+    if (lane == 0) P = -1;
+    if (lane == 63) N = DF_SEG;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < DF_NW; ++k) {
+      if (k < wv) P = max(P, sc[0][k]);
+      if (k > wv) N = min(N, sc[1][k]);
+    }
+  }
+
+  // first pass over the run: the tokens' symbols into the histogram, their bits in the fixed code, the Adler-32 partials
+  int tb = 0;
+  uint32_t s1 = 0, s2 = 0;
+#pragma unroll
+  for (int e = 0; e < DF_RUN; ++e) {
+    if (e >= cnt) continue;
+    const uint32_t byte = (w[e >> 2] >> (8 * (e & 3))) & 0xffu;
+    const int r = df_role(nm, e, base, P, N);
+    if (r < 0) { atomicAdd(&hist[byte], 1u); tb += byte < 144 ? 8 : 9; }
+    else if (r > 0) {
+      uint32_t eb, ex;
+      const uint32_t sym = df_len_code(r, &eb, &ex);
+      atomicAdd(&hist[sym], 1u);
+      tb += (sym < 280 ? 7 : 8) + (int)eb + 5;
+    }
+    s1 += byte;
+    s2 += (uint32_t)(len - base - e) * byte;
+  }
+  s2 %= DF_ADLER;
+  int off = tb, total;
+  {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int y = __shfl_up(off, o);
+      if (lane >= o) off += y;
+      s1 += __shfl_xor(s1, o);
+      s2 += __shfl_xor(s2, o);
+    }
+    if (lane == 63) { sc[2][wv] = off; sc[3][wv] = (int)(s1 % DF_ADLER); sc[4][wv] = (int)(s2 % DF_ADLER); }
+    __syncthreads();
+    off -= tb;
+    total = 0;
+    uint32_t t1 = 0, t2 = 0;
+#pragma unroll
+    for (int k = 0; k < DF_NW; ++k) {
+      if (k < wv) off += sc[2][k];
+      total += sc[2][k];
+      t1 += (uint32_t)sc[3][k];
+      t2 += (uint32_t)sc[4][k];
+    }
+    s1 = t1 % DF_ADLER;
+    s2 = t2 % DF_ADLER;
+  }
+
+  // the segment's code: literal/length lengths and codes, their run-length code, the code-length code
+  const DfdWork wk = {srt, iw, lpar, ipar, idep, lc, nx, &meta[0]};
+  dfd_build<DFD_NLIT, DFD_LIT_LIMIT>(hist, ll, lcode, wk, tid);
+  if (tid == 0) {
+    meta[1] = dfd_num_lit(ll);
+    meta[2] = dfd_rle(ll, meta[1], d, rsym, rext, cc);
+  }
+  __syncthreads();
+  dfd_build<DFD_NCL, DFD_CL_LIMIT>(cc, cl, ccode, wk, tid);
+  const int nl = meta[1], nr = meta[2];
+  const int hbits = dfd_header_bits(cc, cl);
+
+  // second pass: the tokens' bits in the segment's code (a match: + 1 bit of distance)
+  int td = 0;
+#pragma unroll
+  for (int e = 0; e < DF_RUN; ++e) {
+    if (e >= cnt) continue;
+    const uint32_t byte = (w[e >> 2] >> (8 * (e & 3))) & 0xffu;
+    const int r = df_role(nm, e, base, P, N);
+    if (r < 0) td += ll[byte];
+    else if (r > 0) {
+      uint32_t eb, ex;
+      const uint32_t sym = df_len_code(r, &eb, &ex);
+      td += ll[sym] + (int)eb + 1;
+    }
+  }
+  int offd = td, totald = 0;
+  {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int y = __shfl_up(offd, o);
+      if (lane >= o) offd += y;
+    }
+    if (lane == 63) sc[5][wv] = offd;
+    __syncthreads();
+    offd -= td;
+#pragma unroll
+    for (int k = 0; k < DF_NW; ++k) {
+      if (k < wv) offd += sc[5][k];
+      totald += sc[5][k];
+    }
+  }
+
+  // the three forms from their totals; a non-final fixed or dynamic block + the empty stored block 000, pad, 00 00 FF FF
+  const int fixed_bits = 3 + total + 7 + (s.final_ ? 0 : 3);
+  const int fixed_bytes = (fixed_bits + 7) / 8 + (s.final_ ? 0 : 4);
+  const int dyn_bits = hbits + totald + ll[256] + (s.final_ ? 0 : 3);
+  const int dyn_bytes = (dyn_bits + 7) / 8 + (s.final_ ? 0 : 4);
+  const bool dyn = dyn_bytes < fixed_bytes;
+  const int coded_bytes = dyn ? dyn_bytes : fixed_bytes;
+  const bool stored = coded_bytes > 5 + len;
+  const int out_bytes = stored ? 5 + len : coded_bytes;
+  const int out_vecs = (out_bytes + 15) / 16;                 // <= DF_SLOT / 16
+  if (!stored) {
+    for (int i = tid; i < out_vecs * 4 + 2; i += DF_NT) bb[i] = 0;
+    __syncthreads();
+    if (tid == 0 && !s.final_) {                              // FF FF: the last two bytes
+      const int p = 8 * (coded_bytes - 2);
+      atomicOr(&bb[p >> 5], 0xffffu << (p & 31));
+      if ((p & 31) > 16) atomicOr(&bb[(p >> 5) + 1], 0xffffu >> (32 - (p & 31)));
+    }
+    if (dyn) {
+      if (tid == DF_NT - 1) {                                 // the header and EOB: the thread whose run is the first to be short
+        DfdSink hs(bb, 0);
+        dfd_put_header(hs, s.final_, nl, d, cl, ccode, rsym, rext, nr);
+        hs.flush();
+        DfdSink es(bb, hbits + totald);
+        es.put(lcode[256], ll[256]);
+        es.flush();
+      }
+      DfdSink ts(bb, hbits + offd);
+#pragma unroll
+      for (int e = 0; e < DF_RUN; ++e) {
+        if (e >= cnt) continue;
+        const uint32_t byte = (w[e >> 2] >> (8 * (e & 3))) & 0xffu;
+        const int r = df_role(nm, e, base, P, N);
+        if (r < 0) ts.put(lcode[byte], ll[byte]);
+        else if (r > 0) {
+          uint32_t eb, ex;
+          const uint32_t sym = df_len_code(r, &eb, &ex);
+          ts.put((uint32_t)lcode[sym] | ex << ll[sym], ll[sym] + (int)eb + 1);
+        }
+      }
+      ts.flush();
+    } else {
+      if (tid == 0) atomicOr(&bb[0], (uint32_t)s.final_ | 2u);
+      DfdSink ts(bb, 3 + off);
+#pragma unroll
+      for (int e = 0; e < DF_RUN; ++e) {
+        if (e >= cnt) continue;
+        const uint32_t byte = (w[e >> 2] >> (8 * (e & 3))) & 0xffu;
+        int nb;
+        const uint32_t v = df_token(nm, e, base, P, N, byte, d, &nb);
+        ts.put(v, nb);
+      }
+      ts.flush();
+    }
+  } else {
+    // stored block: BFINAL (BTYPE 00, padding), LEN, ~LEN, the raw bytes -- the segment shifted by 5 bytes
+    const uint32_t* x = inw + 4;
+    const uint32_t h4 = ((uint32_t)~len >> 8) & 0xffu;
+    for (int m = tid; m < out_vecs * 4; m += DF_NT) {
+      uint32_t v;
+      if (m == 0) v = (uint32_t)s.final_ | ((uint32_t)len & 0xffffu) << 8 | ((uint32_t)~len & 0xffu) << 24;
+      else {
+        const uint32_t lo = m == 1 ? h4 : m - 2 < len / 4 ? x[m - 2] >> 24 : 0u, hi = m - 1 < len / 4 ? x[m - 1] : 0u;
+        v = lo | hi << 8;
+      }
+      bb[m] = v;
+    }
+  }
+  __syncthreads();
+  uint4* slot4 = reinterpret_cast<uint4*>(slots + (long long)blockIdx.x * DF_SLOT);
+  const uint4* bb4 = reinterpret_cast<const uint4*>(bb);
+  for (int v = tid; v < out_vecs; v += DF_NT) slot4[v] = bb4[v];
+  if (tid == 0) {
+    uint32_t* t = table + 4ll * blockIdx.x;
+    t[0] = (uint32_t)out_bytes; t[1] = s1; t[2] = s2;
+  }
+}
+
 // One workgroup of 1024: thread <-> stream, in chunks of 1024 streams with a running carry.
 __global__ __launch_bounds__(1024) void deflate_offsets_kernel(uint32_t* __restrict__ table, uint8_t* __restrict__ out, uint32_t* __restrict__ offsets,
                                                                int P, int HW, int nso, int nsf) {
@@ -292,20 +557,32 @@ extern "C" int stj_compress_sizes(int B, int Tn, int H, int W, long long* work_b
   return STJ_OK;
 }
 
-extern "C" int stj_compress_waypoints(const uint8_t* Q, void* work, uint8_t* out, uint32_t* offsets, int B, int Tn, int H, int W, hipStream_t stream) {
+static int df_launch(const char* who, const uint8_t* Q, void* work, uint8_t* out, uint32_t* offsets, int B, int Tn, int H, int W, int level,
+                     hipStream_t stream) {
+  if (level != 1 && level != 2) { stj_set_error("%s: level 1 (fixed Huffman code) or 2 (dynamic per segment), got %d", who, level); return STJ_EINVAL; }
   long long nseg, cap; int nso, nsf;
-  const int rc = df_shape("stj_compress_waypoints", B, Tn, H, W, &nseg, &cap, &nso, &nsf);
+  const int rc = df_shape(who, B, Tn, H, W, &nseg, &cap, &nso, &nsf);
   if (rc != STJ_OK) return rc;
   if (((uintptr_t)Q | (uintptr_t)work | (uintptr_t)out | (uintptr_t)offsets) & 15) {
-    stj_set_error("stj_compress_waypoints: 16-byte aligned buffers only");
+    stj_set_error("%s: 16-byte aligned buffers only", who);
     return STJ_EUNSUPPORTED;
   }
   uint32_t* table = reinterpret_cast<uint32_t*>(work);
   uint8_t* slots = reinterpret_cast<uint8_t*>(work) + df_table_bytes(nseg);
   const int HW = H * W;
-  hipLaunchKernelGGL(deflate_encode_kernel, dim3((unsigned)nseg), dim3(DF_NT), 0, stream, Q, slots, table, HW, nso, nsf);
+  if (level == 1) hipLaunchKernelGGL(deflate_encode_kernel, dim3((unsigned)nseg), dim3(DF_NT), 0, stream, Q, slots, table, HW, nso, nsf);
+  else hipLaunchKernelGGL(deflate_encode_dyn_kernel, dim3((unsigned)nseg), dim3(DF_NT), 0, stream, Q, slots, table, HW, nso, nsf);
   hipLaunchKernelGGL(deflate_offsets_kernel, dim3(1), dim3(1024), 0, stream, table, out, offsets, B * 24, HW, nso, nsf);
   hipLaunchKernelGGL(deflate_pack_kernel, dim3((unsigned)nseg), dim3(256), 0, stream, (const uint8_t*)slots, (const uint32_t*)table,
                      (const uint32_t*)offsets, out, HW, nso, nsf);
-  return stj_check_launch("stj_compress_waypoints");
+  return stj_check_launch(who);
+}
+
+extern "C" int stj_compress_waypoints(const uint8_t* Q, void* work, uint8_t* out, uint32_t* offsets, int B, int Tn, int H, int W, hipStream_t stream) {
+  return df_launch("stj_compress_waypoints", Q, work, out, offsets, B, Tn, H, W, 1, stream);
+}
+
+extern "C" int stj_compress_waypoints_level(const uint8_t* Q, void* work, uint8_t* out, uint32_t* offsets, int B, int Tn, int H, int W, int level,
+                                            hipStream_t stream) {
+  return df_launch("stj_compress_waypoints_level", Q, work, out, offsets, B, Tn, H, W, level, stream);
 }

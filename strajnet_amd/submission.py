@@ -9,8 +9,9 @@ The quantisation runs on the device, in front of the device-to-host copy (4 byte
 its own behind any float32 output (stj_quantize_waypoints) or, on the 16-bit inference path, in the epilogue of the kernel that produces
 the logits (stj_outconv_pair_gather_q; STrajNet.predict_quantized picks).  ResultDrain brings the bytes to pinned host memory beside the
 replaying thread.  Compression: either host work (zlib: QuantizedWaypoints.compressed / compress_batch, zlib's own sizes) or on the
-device (compress_waypoints, stj_compress_waypoints: one zlib stream per plane, run-length DEFLATE with the fixed Huffman code in the
-format `compress_reference` states; larger streams, no host work, and only the streams cross to the host).  `quantize_reference` and
+device (compress_waypoints, stj_compress_waypoints: one zlib stream per plane, run-length DEFLATE with the fixed Huffman code, or at
+level 2 with a dynamic Huffman code per segment, in the format `compress_reference` states; larger streams than zlib's default, about
+zlib level 1's at level 2, no host work, and only the streams cross to the host).  `quantize_reference` and
 `compress_reference` are the only CPU code paths here.
 
 dequantize() loses at most 1/510 in probability and 0.5 per flow component (flow beyond [-128, 127] is clipped, as in the format).
@@ -180,13 +181,147 @@ def _pack_bits(vals, nbits, total_bits):
     return out[:(total_bits + 7) // 8]
 
 
-def compress_reference(plane_bytes, d):
-    """The zlib stream stj_compress_waypoints writes for one plane (`plane_bytes`: bytes or a uint8 array; d = 1 for an occupancy plane,
-    2 for a flow plane), byte for byte.  CPU; the statement of the format, for tests and for users without a GPU at hand."""
+# Level 2: the same header, segments, tokens, trailer and empty stored block behind every non-final block; each segment takes the
+# shortest of three forms.  fixed: level 1's bytes for the segment.  dynamic (BTYPE 10, RFC 1951 3.2.7), flush included as for fixed:
+#   literal/length code: the segment's tokens counted per symbol, EOB once -> huffman_code_lengths(counts, 15); HLIT covers up to the
+#     highest used symbol (at least 257 codes).
+#   distance code: d codes (HDIST = d - 1), code d - 1 of length 1, any other 0 -- also in a segment without a match.  zlib takes this
+#     incomplete one-code set; a match writes the single bit 0 for its distance.
+#   the code lengths, literal/length [0, HLIT + 257) then the d distance lengths, as one sequence cut into maximal runs of equal values
+#     (a run may cross the join); a run of r values v: v == 0: while r >= 11 symbol 18 with min(r, 138); then symbol 17 with r if
+#     r >= 3; the rest literal zeros.  v != 0: v once; while the rest >= 3 symbol 16 with min(rest, 6); the rest literal v.
+#   code-length code: huffman_code_lengths(counts of the 19 symbols, 7); HCLEN up to the last non-zero length in the order 16, 17, 18,
+#     0, 8, 7, ..., at least 4.  At least two of its symbols are always in use (an unused literal symbol gives a zero next to non-zero
+#     lengths).
+# fixed if len(fixed) <= len(dynamic), else dynamic; if the form taken exceeds 5 + len bytes the segment is stored.  So a level-2 segment
+# is never longer than its level-1 segment and the capacity bound holds.
+# Resolutions of what the rules above leave open: a code over a single used symbol gives that symbol length 1 (it occurs in neither of
+# the two codes of a stream, only through huffman_code_lengths); the depth histogram of step 4 is built even when no depth exceeds the
+# limit, so lengths are ALWAYS handed out by sorted order (equal multiset, and equal counts get lengths that never decrease with the
+# symbol number).
+
+_CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
+_LEN_BASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
+_LEN_EXTRA = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
+_LEN_CODE = {m: max(i for i in range(29) if _LEN_BASE[i] <= m and (i == 28 or m < 258)) for m in range(3, 259)}
+
+
+def huffman_code_lengths(counts, limit):
+    """Code lengths (0: unused) of the length-limited Huffman code of level 2 over `counts`:
+      1. the used symbols sorted ascending by (count, symbol);
+      2. the Huffman tree by the two-queue method over that order -- on equal weight a leaf before an internal node, internal nodes in
+         creation order;
+      3. a symbol's length is the depth of its leaf;
+      4. cnt[l]: the histogram of the lengths, those above `limit` counted at `limit`; while sum cnt[l] 2^(limit - l) > 2^limit:
+         cnt[limit] -= 1, and with the largest l < limit that has cnt[l] > 0: cnt[l] -= 1, cnt[l + 1] += 2 (each round lowers the sum by 1);
+      5. the lengths 1, 2, ... of the histogram go, in increasing order, to the symbols in DESCENDING sorted order."""
+    order = sorted((int(c), s) for s, c in enumerate(counts) if c > 0)
+    n, out = len(order), [0] * len(counts)
+    if n == 0:
+        return out
+    if n == 1:
+        out[order[0][1]] = 1
+        return out
+    weight = [c for c, _ in order]                      # nodes 0 .. n - 1: the leaves; n .. 2n - 2: internal, in creation order
+    parent = [0] * (2 * n - 1)
+    li, ii = 0, n
+    for k in range(n, 2 * n - 1):
+        w = 0
+        for _ in range(2):
+            if li < n and (ii >= k or weight[li] <= weight[ii]):
+                w, parent[li], li = w + weight[li], k, li + 1
+            else:
+                w, parent[ii], ii = w + weight[ii], k, ii + 1
+        weight.append(w)
+    depth = [0] * (2 * n - 1)
+    for k in range(2 * n - 3, -1, -1):
+        depth[k] = depth[parent[k]] + 1
+    cnt = [0] * (limit + 1)
+    for k in range(n):
+        cnt[min(depth[k], limit)] += 1
+    while sum(cnt[l] << (limit - l) for l in range(1, limit + 1)) > 1 << limit:
+        cnt[limit] -= 1
+        l = max(l for l in range(1, limit) if cnt[l] > 0)
+        cnt[l] -= 1
+        cnt[l + 1] += 2
+    q = n - 1
+    for l in range(1, limit + 1):
+        for _ in range(cnt[l]):
+            out[order[q][1]] = l
+            q -= 1
+    return out
+
+
+def _canonical_codes(lengths):
+    """RFC 1951 3.2.2, each code bit-reversed: as it enters the LSB-first bit stream."""
+    mx = max(lengths)
+    bl = [0] * (mx + 2)
+    for l in lengths:
+        bl[l] += l > 0
+    nxt, code = [0] * (mx + 2), 0
+    for b in range(1, mx + 1):
+        code = (code + bl[b - 1]) << 1
+        nxt[b] = code
+    out = []
+    for l in lengths:
+        out.append(_rev(nxt[l], l) if l else 0)
+        nxt[l] += l > 0
+    return out
+
+
+def dynamic_block_header(lit_counts, d, final):
+    """The dynamic block's header for the 286 literal/length counts of a segment (EOB included): (literal/length code lengths, their
+    codes as they enter the bit stream, the header's tokens as (values, bit counts) from BFINAL up to the last code length)."""
+    ll = huffman_code_lengths(lit_counts, 15)
+    nl = max(257, max(s for s in range(286) if ll[s]) + 1)
+    seq = ll[:nl] + [0] * (d - 1) + [1]
+    rle, i = [], 0                                      # (code-length symbol, extra value, extra bits)
+    while i < len(seq):
+        v, r = seq[i], 1
+        while i + r < len(seq) and seq[i + r] == v:
+            r += 1
+        i += r
+        if v == 0:
+            while r >= 11:
+                t = min(r, 138)
+                rle.append((18, t - 11, 7))
+                r -= t
+            if r >= 3:
+                rle.append((17, r - 3, 3))
+                r = 0
+        else:
+            rle.append((v, 0, 0))
+            r -= 1
+            while r >= 3:
+                t = min(r, 6)
+                rle.append((16, t - 3, 2))
+                r -= t
+        rle += [(v, 0, 0)] * r
+    cc = [0] * 19
+    for s, _, _ in rle:
+        cc[s] += 1
+    assert sum(c > 0 for c in cc) >= 2
+    cl = huffman_code_lengths(cc, 7)
+    ccode = _canonical_codes(cl)
+    ncl = max(4, max(j for j in range(19) if cl[_CL_ORDER[j]]) + 1)
+    vals = [int(final) | 4, nl - 257, d - 1, ncl - 4] + [cl[_CL_ORDER[j]] for j in range(ncl)]
+    nbits = [3, 5, 5, 4] + [3] * ncl
+    for s, ev, eb in rle:
+        vals.append(ccode[s] | ev << cl[s])
+        nbits.append(cl[s] + eb)
+    return ll, _canonical_codes(ll), vals, nbits
+
+
+def compress_reference(plane_bytes, d, level=1, forms=None):
+    """The zlib stream stj_compress_waypoints (level 1) / stj_compress_waypoints_level writes for one plane (`plane_bytes`: bytes or a
+    uint8 array; d = 1 for an occupancy plane, 2 for a flow plane), byte for byte.  CPU; the statement of the format, for tests and for
+    users without a GPU at hand.  `forms`: a list that receives, per segment, the form it took (its BTYPE: 0 stored, 1 fixed, 2 dynamic)."""
     x = np.frombuffer(bytes(plane_bytes), np.uint8) if not isinstance(plane_bytes, np.ndarray) else plane_bytes.reshape(-1).view(np.uint8)
     n, S = x.size, DEFLATE_SEGMENT
     if n == 0 or d not in (1, 2):
         raise ValueError('compress_reference: a non-empty plane and d in (1, 2)')
+    if level not in (1, 2):
+        raise ValueError('compress_reference: level 1 or 2')
     matchable = np.zeros(n, bool)
     matchable[d:] = x[d:] == x[:-d]
     dist_v = _rev(d - 1, 5)
@@ -195,6 +330,7 @@ def compress_reference(plane_bytes, d):
         seg, m = x[s0:s0 + S], matchable[s0:s0 + S]
         L, final = seg.size, s0 + S >= n
         vals, nbits = _LIT_V[seg].copy(), _LIT_N[seg].copy()
+        mlen = np.zeros(L, np.int64)                                # level 2: the length of the match that starts at a byte
         edge = np.flatnonzero(np.diff(np.concatenate([[False], m, [False]]).astype(np.int8)))
         for a, e in zip(edge[0::2], edge[1::2]):                   # the stretches [a, e) of matchable bytes
             pos, rest = int(a), int(e - a)
@@ -203,16 +339,36 @@ def compress_reference(plane_bytes, d):
                 vals[pos] = _LEN_V[ml] | (dist_v << _LEN_N[ml])
                 nbits[pos] = _LEN_N[ml] + 5
                 nbits[pos + 1:pos + ml] = 0
+                mlen[pos] = ml
                 pos, rest = pos + ml, rest - ml
         keep = nbits > 0
         vals = np.concatenate([[np.uint64(int(final) | 2)], vals[keep]]).astype(np.uint64)          # BFINAL, BTYPE 01 in front; EOB = 7 zero bits
         nbits = np.concatenate([[3], nbits[keep]])
         bits = int(nbits.sum()) + 7 + (0 if final else 3)                                         # non-final: + the empty stored block's 000
-        fixed = _pack_bits(vals, nbits, bits).tobytes() + (b'' if final else b'\x00\x00\xff\xff')
-        if len(fixed) > 5 + L:
-            out.append(bytes([int(final), L & 255, L >> 8, ~L & 255, (~L >> 8) & 255]) + seg.tobytes())
-        else:
-            out.append(fixed)
+        block, form = _pack_bits(vals, nbits, bits).tobytes() + (b'' if final else b'\x00\x00\xff\xff'), 1
+        if level == 2:
+            tok, tml = seg[keep].astype(np.int64), mlen[keep]
+            lc = np.array([_LEN_CODE.get(int(ml), 0) for ml in tml], np.int64)
+            sym = np.where(tml > 0, 257 + lc, tok)
+            counts = np.bincount(sym, minlength=286)
+            counts[256] = 1
+            ll, code, hv, hn = dynamic_block_header(counts, d, final)
+            ll, code = np.array(ll, np.int64), np.array(code, np.uint64)
+            eb = np.where(tml > 0, np.array(_LEN_EXTRA, np.int64)[lc], 0)
+            ev = np.where(tml > 0, tml - np.array(_LEN_BASE, np.int64)[lc], 0).astype(np.uint64)
+            tv = code[sym] | ev << ll[sym].astype(np.uint64)          # a match: + the distance's single bit 0
+            tn = ll[sym] + eb + (tml > 0)
+            dv = np.concatenate([np.array(hv, np.uint64), tv, [code[256]]]).astype(np.uint64)
+            dn = np.concatenate([np.array(hn, np.int64), tn, [ll[256]]])
+            dbits = int(dn.sum()) + (0 if final else 3)
+            dyn = _pack_bits(dv, dn, dbits).tobytes() + (b'' if final else b'\x00\x00\xff\xff')
+            if len(dyn) < len(block):
+                block, form = dyn, 2
+        if len(block) > 5 + L:
+            block, form = bytes([int(final), L & 255, L >> 8, ~L & 255, (~L >> 8) & 255]) + seg.tobytes(), 0
+        out.append(block)
+        if forms is not None:
+            forms.append(form)
     out.append(zlib.adler32(x.tobytes()).to_bytes(4, 'big'))
     return b''.join(out)
 
@@ -277,9 +433,13 @@ class CompressedWaypoints:
         return [tuple(raw[cut[3 * k + i]:cut[3 * k + i + 1]] for i in range(3)) for k in range(self.Tn)]
 
 
-def compress_waypoints(qw, out=None):
+def compress_waypoints(qw, out=None, level=1):
     """A device QuantizedWaypoints -> CompressedWaypoints (stj_compress_waypoints: no host synchronisation, no allocation with `out`
-    given -- a CompressedWaypoints.empty of the same shape, written in place -- so the call can be captured in a graph)."""
+    given -- a CompressedWaypoints.empty of the same shape, written in place -- so the call can be captured in a graph).  level 1: the
+    fixed Huffman code; level 2: per segment the shortest of stored, fixed and a dynamic Huffman code of its own
+    (stj_compress_waypoints_level; compress_reference(level=2)): smaller streams from the same three launches' worth of work."""
+    if level not in (1, 2):
+        raise ValueError(f'compress_waypoints: level 1 or 2, got {level!r}')
     if not qw.buf.is_cuda:
         raise RuntimeError('compress_waypoints: CUDA (ROCm) buffers only: the HIP path has no CPU fallback (CPU: compress_reference, '
                            'or zlib through QuantizedWaypoints.compressed)')
@@ -291,7 +451,10 @@ def compress_waypoints(qw, out=None):
         if (out.work is None or not out.buf.is_cuda or out.B != B or out.Tn != qw.Tn or out.buf.numel() < cap or out.work.numel() < work
                 or out.buf.device != qw.buf.device):
             raise ValueError('compress_waypoints: `out` must be a CompressedWaypoints.empty() of the same shape on the same device')
-    call('stj_compress_waypoints', _p(qw.buf), _p(out.work), _p(out.buf), _p(out.offsets), B, qw.Tn, qw.H, qw.W, _st())
+    if level == 1:
+        call('stj_compress_waypoints', _p(qw.buf), _p(out.work), _p(out.buf), _p(out.offsets), B, qw.Tn, qw.H, qw.W, _st())
+    else:
+        call('stj_compress_waypoints_level', _p(qw.buf), _p(out.work), _p(out.buf), _p(out.offsets), B, qw.Tn, qw.H, qw.W, level, _st())
     return out
 
 

@@ -3,15 +3,15 @@
 
   --mode rows   scenes/s for (a) no read-back (bench.py --infer's figure), (b) the float32 output copied to pinned memory each step,
                 (c) quantised output + ResultDrain, (d) as (c) plus zlib compression of every scene on 16 threads, (e) the graph that
-                also compresses on the device (GraphedForward(quantized=True, compressed=True)) + ResultDrain, no host zlib; bytes per
-                scene of (d) and (e) side by side
+                also compresses on the device (GraphedForward(quantized=True, compressed=True, compress_level=--level)) + ResultDrain,
+                no host zlib; bytes per scene of (d) and (e) side by side
   --mode ab     GraphedForward(quantized=True) with the quantising gather (stj_outconv_pair_gather_q) against the same graph built from
                 stj_outconv_pair_gather + stj_quantize_waypoints, alternating, --pairs times; each build is timed TWICE in a row per
                 visit, so the spread of repeated runs of the same build is measured in the same call
   --mode trace  a few replays of both quantised graphs and nothing else: the workload of a `rocprofv3 --kernel-trace --stats` run
   --sparse      (instead of a mode) random weights give noise-like planes, which the device-side compressor mostly stores; this fills a
                 static quantised buffer ONCE with synthetic sparse planes (seeded blobs on a zero background) and times
-                stj_compress_waypoints (captured) + ResultDrain alone against host compress_batch of the same bytes on --threads threads.
+                stj_compress_waypoints at --level (captured) + ResultDrain alone against host compress_batch of the same bytes on --threads threads.
                 With --trace-only: a few replays of the captured compression and nothing else, for a kernel trace.
 
 Every timing is a host clock around `--steps` replays that end in a device synchronise, after `--warmup` replays, profiler off.
@@ -36,6 +36,7 @@ ap.add_argument('--chunk-bytes', type=int, default=3 << 19)
 ap.add_argument('--sparse', action='store_true')
 ap.add_argument('--noise', action='store_true', help='with --sparse: uniformly random planes instead (the stored fallback everywhere)')
 ap.add_argument('--trace-only', action='store_true')
+ap.add_argument('--level', type=int, default=1, choices=[1, 2], help='compression level of row (e) and of --sparse: 1 fixed, 2 dynamic Huffman code')
 a = ap.parse_args()
 
 import bench
@@ -83,17 +84,17 @@ if a.sparse:
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        compress_waypoints(qw, out=cw)
+        compress_waypoints(qw, out=cw, level=a.level)
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
-        compress_waypoints(qw, out=cw)
+        compress_waypoints(qw, out=cw, level=a.level)
     if a.trace_only:
         for _ in range(10):
             g.replay()
         torch.cuda.synchronize()
-        print(json.dumps({'mode': 'sparse-trace', 'batch': B, 'replays': 10 + 1, 'noise': a.noise, 'input_bytes': qw.buf.numel(),
+        print(json.dumps({'mode': 'sparse-trace', 'batch': B, 'level': a.level, 'replays': 10 + 1, 'noise': a.noise, 'input_bytes': qw.buf.numel(),
                           'stream_bytes': cw.nbytes}), flush=True)
         sys.exit(0)
     drain = ResultDrain(cw, depth=3, chunk_bytes=a.chunk_bytes)
@@ -137,7 +138,7 @@ if a.sparse:
     host_rate = B * reps / (time.perf_counter() - t0)
     pool.shutdown()
     zl = sum(len(s) for scene in comp for wp in scene for s in wp)
-    print(json.dumps({'mode': 'sparse', 'noise': a.noise, 'batch': B, 'steps': a.steps, 'warmup': a.warmup, 'threads': a.threads,
+    print(json.dumps({'mode': 'sparse', 'noise': a.noise, 'batch': B, 'level': a.level, 'stream_bytes': cw.nbytes, 'steps': a.steps, 'warmup': a.warmup, 'threads': a.threads,
                       'device_compress_drain_scenes_per_s': round(dev_rate, 1), 'host_zlib_scenes_per_s': round(host_rate, 1),
                       'compress_ms_per_batch': round(e0.elapsed_time(e1) / 20, 4),
                       'raw_bytes_per_scene': qw.buf.shape[1], 'device_stream_bytes_per_scene': cw.nbytes / B,
@@ -148,10 +149,10 @@ model = STrajNet(bench.CFG256, fg_msa=True, fg=True, large_ogm=False, dtype=torc
 x = bench.synth_batch(B, 1234, dev, 256)
 
 
-def graph(quantized, fused=True, compressed=False):
+def graph(quantized, fused=True, compressed=False, level=1):
     model.fused_quantize = fused
     try:
-        return GraphedForward(model, x, pipeline_agents=True, quantized=quantized, compressed=compressed)
+        return GraphedForward(model, x, pipeline_agents=True, quantized=quantized, compressed=compressed, compress_level=level)
     finally:
         model.fused_quantize = True
 
@@ -226,7 +227,7 @@ if a.mode == 'rows':
         drain.close()
     res['c_bytes_per_scene'] = gq.out.buf.shape[1]
     del gq
-    ge = graph(True, compressed=True)
+    ge = graph(True, compressed=True, level=a.level)
     drain = ResultDrain(ge.out, depth=3, chunk_bytes=a.chunk_bytes)
     pending, sizes = [0], []
 
@@ -247,8 +248,9 @@ if a.mode == 'rows':
             consume_e()
     res['e_compressed_drain'] = timed(step_e, finish_e)
     res['e_compressed_bytes_per_scene'] = sum(sizes) / len(sizes) / B
+    res['stream_bytes'] = ge.out.nbytes
     drain.close()
-    print(json.dumps({'mode': 'rows', 'batch': B, 'steps': a.steps, 'warmup': a.warmup, 'unit': 'scenes/s',
+    print(json.dumps({'mode': 'rows', 'batch': B, 'level': a.level, 'steps': a.steps, 'warmup': a.warmup, 'unit': 'scenes/s',
                       **{k: round(v, 1) for k, v in res.items()}}), flush=True)
 elif a.mode == 'ab':
     g_f, g_u = graph(True, True), graph(True, False)
