@@ -586,6 +586,29 @@ int stj_pack_sparse_commit(const float* src, const uint32_t* offs_stage, const i
                            int y0, int x0, int Ho, int Wo, hipStream_t stream);
 int stj_pool_put_raw(const void* src, int itemsize, const int* ok, const int* slots, int N, void* pool, int B, long long n, hipStream_t stream);
 
+/* A shuffle window over such a pool (csrc/window.hip; the semantics are stated by ShuffleWindow.reference and
+ * PoolLayout.replace_packed_reference in strajnet_amd/data.py).
+ * stj_pool_draw: perm int32 [N] and idx int32 [B] ON THE DEVICE, u uint32 [B] random words on the device.  The live slots are
+ * perm[tail : tail + n_live) (circular mod N); for i = 0 .. B - 1: j = (u[i] * (n_live - i)) >> 32, swap perm[(tail + i) % N] and
+ * perm[(tail + i + j) % N], idx[i] = perm[(tail + i) % N] clamped to [0, N - 1].  One workgroup, one lane.  STJ_EINVAL with nothing launched
+ * for n_live < B, B < 0, N < 1 or tail outside [0, N); STJ_OK with nothing launched for B == 0.
+ * stj_pool_admit_packed (one launch per sparse key, all of them before any put): offs_src uint32 [B][nblk + 1], the scene-relative offs rows
+ * as pack_sparse writes them, nblk = ceil(n / 8192); src_base int64 [B + 1] the scenes' first words in the staged values.
+ * ok[b] = (first ? 0 <= slots[b] < N : ok[b]) && offs_src[b][0] == 0 && the row does not decrease && no block holds more present words than
+ * elements && total == src_base[b + 1] - src_base[b] && total <= val_base[s + 1] - val_base[s], total = offs_src[b][nblk].
+ * stj_pool_put_vals: scene b's words vals_src[src_base[b] .. src_base[b + 1]) -> vals[val_base[s] ..), s = slots[b]; 64-bit indices, every
+ * store inside [val_base[s], min(val_base[s + 1], n_vals)) whatever src_base and val_base hold; vals_src is read inside
+ * [src_base[b], src_base[b + 1]) only.  A scene with ok[b] == 0 or a slot outside [0, N) is skipped, never clamped.  The fixed-length rows
+ * of a packed record (bits words, mask and offs rows as itemsize 4, raw rows) go through stj_pool_put_raw.
+ * STJ_EUNSUPPORTED: misaligned pointers (4-byte words, slots, ok, perm, idx; 8-byte src_base / val_base), n % 32 != 0, n >= 2^32, nblk not
+ * ceil(n / 8192), more workgroups than a launch takes; STJ_EINVAL: NULL, negative sizes.  One launch each on `stream`: no host
+ * synchronisation, no allocation, no atomics. */
+int stj_pool_draw(int* perm, int N, int tail, int n_live, const uint32_t* u, int* idx, int B, hipStream_t stream);
+int stj_pool_admit_packed(const uint32_t* offs_src, int nblk, long long n, const long long* src_base, const long long* val_base,
+                          const int* slots, int N, int* ok, int B, int first, hipStream_t stream);
+int stj_pool_put_vals(const uint32_t* vals_src, const long long* src_base, const int* ok, const int* slots, int N,
+                      const long long* val_base, uint32_t* vals, long long n_vals, int B, hipStream_t stream);
+
 /* trajNet input plumbing (trajNet.py:125-140), one launch: obs [B,n_obs,Tn,8] and occ [B,n_occ,Tn,8] (f32, 16-byte aligned) ->
  * x5 [B*A*Tn,5] node features, v3 [B*A,3] vector features of step 0, vt [B*A,Tn] int32 step-valid (feature 0 != 0), cmi [B*A] int32 /
  * cmf [B*A] (type T) agent-valid (any step valid); A = n_obs + n_occ, obs rows first. */

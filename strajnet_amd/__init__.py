@@ -14,3 +14,4 @@ from .evaluate import Mean, OGMFlowMetrics, print_metrics, eval_step     # noqa:
 from .submission import (QuantizedWaypoints, ResultDrain, quantize_waypoints, quantize_reference,     # noqa: F401
                          compress_batch, compression_pool, CompressedWaypoints, compress_waypoints, compress_reference,
                          DEFLATE_SEGMENT)
+from .data import (ResidentPool, ResidentFeed, PoolLayout, PoolWriter, PoolSampler, ShuffleWindow, WindowFeed)     # noqa: F401

@@ -22,6 +22,10 @@ with no upload per step, `PoolSampler` shuffles on the device.  `PoolLayout.refe
 Pool scenes are replaced in place from the reference's own unpacked records: `ResidentPool.empty` allocates zero-filled slots,
 `PoolWriter` (pool.writer(B)) uploads the raw bytes and packs them on the device (stj_pack_bits / stj_pack_sparse_count / stj_pool_admit /
 stj_pack_sparse_commit / stj_pool_put_raw); `PoolLayout.replace_reference` states that in NumPy.
+A shuffle buffer in HBM over a stream of any length: `ShuffleWindow` (pool.window(B, source)) draws batches from the live slots on the device
+(stj_pool_draw) and refills consumed slots from packed records on a worker thread and a stream of its own (stj_pool_admit_packed /
+stj_pool_put_raw / stj_pool_put_vals); `WindowFeed` has HostFeed's protocol, `PoolWriter.put_packed` is the synchronous form;
+`ShuffleWindow.reference` and `PoolLayout.replace_packed_reference` state the semantics.
 """
 import ctypes
 import struct
@@ -743,6 +747,36 @@ def _scene_words(x):
     return None if b.size % 4 else b.view('<u4')
 
 
+def _packed_parts(ex, b, grid, out, test, names, entries):
+    """The arrays of ONE pack_example record as a pool's keys hold them: [(key, parts)] with parts (words,) for a bits key, check_sparse's
+    (mask, offs, vals) for a sparse key and (the record's own elements,) for a raw key.  ValueError naming key and scene `b` for a missing
+    or malformed feature, or a key whose kind or size is not the record's."""
+    res = []
+    for name, (dtype, shape, crop, scale) in feature_spec(grid, out, test).items():
+        key = names.get(name, name)
+        e = entries.get(key)
+        want = PACKED_KIND.get(name, 'raw')
+        n = int(np.prod(decoded_shape(shape, crop)))
+        if e is None or e['kind'] != want or e['n'] != n or (want == 'raw' and e['dtype'] != dtype):
+            raise ValueError(f"PoolLayout[{key!r}]: holds {None if e is None else (e['kind'], e['n'])}, a packed record gives {want} scenes of {n} elements")
+        try:
+            if want == 'bits':
+                w = _scene_words(ex[name + '/bits'])
+                if w is None or w.size != n // 32:
+                    raise ValueError(f"{len(ex[name + '/bits'])} bytes of bits, expected {n // 8}")
+                parts = (w,)
+            elif want == 'sparse':
+                parts = check_sparse(*(ex[f'{name}/{p}'] for p in ('mask', 'offs', 'vals')), n, 'stream')
+            else:
+                parts = (np.ascontiguousarray(_decoded(ex[name], dtype, shape, crop)).reshape(-1),)
+        except KeyError as err:
+            raise ValueError(f'PoolLayout[{key!r}] scene {b}: the record lacks the feature {err}') from None
+        except (ValueError, TypeError) as err:
+            raise ValueError(f'PoolLayout[{key!r}] scene {b}: {err}') from None
+        res.append((key, parts))
+    return res
+
+
 class PoolLayout:
     """N packed scenes laid out as stj_gather_bits / stj_gather_sparse / stj_gather_raw read them; NumPy only, no device.
 
@@ -977,6 +1011,40 @@ class PoolLayout:
                     e['data'][s] = parts[0]
         return landed
 
+    def replace_packed_reference(self, slots, packed_examples, grid=512, out=256, test=False, names=None):
+        """replace_reference for records that pack_example has already rewritten: the semantics of PoolWriter.put_packed and of a
+        ShuffleWindow's refill in NumPy.  Scene b goes to slot slots[b]; it is admitted iff 0 <= slots[b] < N and, for every sparse key,
+        offs[-1] <= val_base[s + 1] - val_base[s]; all-or-nothing across keys, and what an admitted scene writes is what replace_reference
+        writes, so replace_packed_reference(slots, [pack_example(e)]) leaves the layout byte-identical to replace_reference(slots, [e]).
+        Every sparse stream is validated with check_sparse: a malformed record raises ValueError naming key and scene, before any slot
+        changes.  -> [1 | 0] per scene."""
+        names = POOL_NAMES if names is None else names
+        slots = [int(s) for s in slots]
+        examples = list(packed_examples)
+        if len(slots) != len(examples):
+            raise ValueError(f'replace_packed_reference: {len(slots)} slots for {len(examples)} scenes')
+        if len(set(slots)) != len(slots):
+            raise ValueError(f'replace_packed_reference: duplicate slots in {slots}')
+        plan = []
+        for b, ex in enumerate(examples):
+            plan.append([(key, self.entries[key], parts) for key, parts in _packed_parts(ex, b, grid, out, test, names, self.entries)])
+        landed = []
+        for s, new in zip(slots, plan):
+            fits = 0 <= s < self.N and all(parts[2].size <= int(e['val_base'][s + 1] - e['val_base'][s]) for _, e, parts in new if e['kind'] == 'sparse')
+            landed.append(int(fits))
+            if not fits:
+                continue
+            for key, e, parts in new:
+                if e['kind'] == 'bits':
+                    e['words'][s] = parts[0]
+                elif e['kind'] == 'sparse':
+                    v0 = int(e['val_base'][s])
+                    e['mask'][s], e['offs'][s] = parts[0], parts[1]
+                    e['vals'][v0:v0 + parts[2].size] = parts[2]
+                else:
+                    e['data'][s] = parts[0]
+        return landed
+
     def check_index(self, idx):
         """A host index list: ValueError unless every index is in [0, N).  -> int64 array."""
         idx = np.asarray(idx, np.int64).reshape(-1)
@@ -1066,8 +1134,8 @@ class ResidentPool:
     Scenes are replaced in place from the reference's own unpacked records: ResidentPool.empty(N, ...) allocates zero-filled slots (a sparse
     key's slot holds `capacity` value words), pool.writer(B) returns a PoolWriter whose put(slots, examples) uploads the raw bytes and packs
     them on the device (stj_pack_bits / stj_pack_sparse_* / stj_pool_put_raw) -- a rolling window over a dataset larger than HBM.
-    Out of scope: replacement from already-packed records (a scatter copy with no packing); a refill overlapped with the running step
-    on a stream of its own (commit runs on the current stream, in front of the gathers); any policy for which slots to evict."""
+    put_packed(slots, packed_examples) does the same from records that are already packed (a scatter copy with no packing), and
+    pool.window(B, source) is a ShuffleWindow: consumed slots refilled on a stream of its own while the step runs."""
 
     def __init__(self, layout, device='cuda', chunk_bytes=3 << 19):
         dev = torch.device(device)
@@ -1204,6 +1272,10 @@ class ResidentPool:
     def sampler(self, batch_size, shuffle=True, seed=0, drop_last=True):
         """PoolSampler over this pool's scenes, on its device."""
         return PoolSampler(self.N, batch_size, self.dev, shuffle, seed, drop_last)
+
+    def window(self, batch_size, source, **kw):
+        """ShuffleWindow(self, batch_size, source, **kw): this pool as the shuffle buffer of a stream of records."""
+        return ShuffleWindow(self, batch_size, source, **kw)
 
 
 class ResidentFeed:
@@ -1380,3 +1452,552 @@ class PoolWriter:
             else:
                 call('stj_pool_put_raw', _p(self.raw[name]), ITEMSIZE[e['dtype']], ok, sl, N, _p(d['data']), B, e['n'], st)
         return self.ok
+
+    # ---- records that pack_example has already rewritten: a scatter copy with no packing
+    def _packed_stage(self):
+        if getattr(self, 'packed', None) is None:
+            self.packed = _PackedStage(self.pool, self.B, self.chunk)
+            self._pup, self._pdone, self._ppending = torch.cuda.Event(), torch.cuda.Event(), False
+        return self.packed
+
+    def put_packed(self, slots, packed_examples):
+        """put() for B pack_example records: the packed planes go up as they are stored (a sparse plane: only its used words) and are
+        copied into the slots -- stj_pool_admit_packed per sparse key, then stj_pool_put_raw for the fixed-length rows and stj_pool_put_vals
+        for the value words.  PoolLayout.replace_packed_reference states the semantics.  Every stream is checked on the host first
+        (check_sparse; ValueError naming key and scene, nothing launched).  -> writer.ok."""
+        examples = list(packed_examples)
+        if len(examples) != self.B:
+            raise ValueError(f'PoolWriter: {len(examples)} records for a writer of {self.B} scenes')
+        st = self._packed_stage()
+        parsed = [st.check(ex, b) for b, ex in enumerate(examples)]
+        self._set_slots(slots)
+        self.stage_packed(parsed)
+        return self.commit_packed()
+
+    def stage_packed(self, parsed):
+        """The upload half of put_packed(): parsed = [writer.packed.check(record, b)] into the device staging writer.packed.dev through
+        pinned memory on the copy stream; the current stream waits for it."""
+        st = self._packed_stage()
+        if len(parsed) != self.B:
+            raise ValueError(f'PoolWriter: {len(parsed)} records for a writer of {self.B} scenes')
+        if self._ppending:
+            self._pup.synchronize()
+        st.begin()
+        for b, p in enumerate(parsed):
+            st.fill(b, p)
+        main = torch.cuda.current_stream(self.dev)
+        self._pdone.record(main)
+        with torch.cuda.stream(self.copy):
+            self.copy.wait_event(self._pdone)
+            st.upload(self.B)
+            self._pup.record(self.copy)
+        self._ppending = True
+        main.wait_event(self._pup)
+
+    def commit_packed(self, slots=None):
+        """Copies what writer.packed.dev holds into the slots writer.slots names.  Launches only, on the current stream: capturable like
+        commit() (stage_packed() between replays)."""
+        if slots is not None:
+            self._set_slots(slots)
+        self.pool._await_upload()
+        self._packed_stage().launch(_p(self.slots), self.B, _p(self.ok))
+        return self.ok
+
+
+def _pieces(dst, src, count, chunk_bytes):
+    """dst[:count] <- src[:count] (flat tensors, host to device) in copies of at most chunk_bytes, on the current stream."""
+    step = max(1, chunk_bytes // src.element_size())
+    for i in range(0, count, step):
+        j = min(count, i + step)
+        dst[i:j].copy_(src[i:j], non_blocking=True)
+
+
+class _PackedStage:
+    """The staging of up to B pack_example records on their way into the slots of a pool: per record feature pinned host arrays and
+    their device twins, allocated once, in the batch format of SparseHost and decode_batch_packed -- bits words [B][n / 32]; a sparse key's
+    mask [B][n / 32], scene-relative offs [B][nblk + 1], src_base int64 [B + 1] and vals, the scenes' value words back to back; the raw
+    rows [B][nbytes].  vals holds B x the slot capacity: a record that no slot can hold is never staged.
+    check(record, b) validates one record on the host, begin() / fill(b, parsed) write the pinned side, upload(count) copies the first
+    `count` scenes to the device on the current stream, launch(slots, count, ok) issues the admits and then the puts there."""
+
+    def __init__(self, pool, B, chunk_bytes=3 << 19):
+        lay = pool.layout
+        if lay.geometry is None:
+            raise ValueError('packed staging: a pool laid out by PoolLayout.empty / from_examples (or ResidentPool.empty) only: the keys of a '
+                             'hand-built layout do not say which record feature they hold')
+        self.pool, self.B, self.dev, self.chunk = pool, int(B), pool.dev, max(1, int(chunk_bytes))
+        self.geometry = lay.geometry
+        rows = max(self.B, 1)
+        self.feats, self.capacity, self.host, self.dev_bufs = [], {}, {}, {}
+        grid, out, test, names = lay.geometry
+        for name, (dtype, shape, crop, scale) in feature_spec(grid, out, test).items():
+            key = names.get(name, name)
+            e = lay.entries.get(key)
+            kind = PACKED_KIND.get(name, 'raw')
+            n = int(np.prod(decoded_shape(shape, crop)))
+            if e is None or e['kind'] != kind or e['n'] != n or (kind == 'raw' and (e['dtype'] != dtype or crop is not None)):
+                raise ValueError(f"packed staging: pool key {key!r} is {None if e is None else (e['kind'], e['n'])}, packed records give {kind} "
+                                 f'scenes of {n} elements')
+            self.feats.append((name, key, e, kind, n))
+            if kind == 'bits':
+                sizes = {'bits': (rows * (n // 32), torch.int32)}
+            elif kind == 'sparse':
+                cap = int(e['capacity']) if lay.device_only else int(np.diff(e['val_base']).min())
+                self.capacity[key] = cap
+                sizes = {'mask': (rows * (n // 32), torch.int32), 'offs': (rows * (-(-n // SPARSE_BLOCK) + 1), torch.int32),
+                         'base': (rows + 1, torch.int64), 'vals': (max(rows * cap, 1), torch.int32)}
+            else:
+                sizes = {'raw': (rows * n * ITEMSIZE[dtype], torch.uint8)}
+            for part, (count, dt) in sizes.items():
+                self.host[name, part] = torch.zeros((max(count, 1),), dtype=dt).pin_memory()
+                self.dev_bufs[name, part] = torch.zeros((max(count, 1),), dtype=dt, device=self.dev)
+        self.dev = pool.dev
+        self._base = {}
+
+    def check(self, ex, b=0):
+        """One pack_example record -> its arrays as fill() takes them; ValueError naming key and scene for a malformed one."""
+        grid, out, test, names = self.geometry
+        return _packed_parts(ex, b, grid, out, test, names, self.pool.layout.entries)
+
+    def misfit(self, parsed):
+        """None, or why no slot of the pool holds this record: a sparse key with more value words than a slot's capacity."""
+        for (name, key, e, kind, n), (_, parts) in zip(self.feats, parsed):
+            if kind == 'sparse' and parts[2].size > self.capacity[key]:
+                return f'{key}: {parts[2].size} value words, a slot holds {self.capacity[key]}'
+        return None
+
+    def begin(self):
+        self._base = {name: [0] for name, _, _, kind, _ in self.feats if kind == 'sparse'}
+
+    def fill(self, b, parsed):
+        for (name, key, e, kind, n), (_, parts) in zip(self.feats, parsed):
+            if kind == 'bits':
+                _put(self.host[name, 'bits'], b * (n // 32), parts[0])
+            elif kind == 'sparse':
+                base = self._base[name]
+                if len(base) != b + 1:
+                    raise ValueError(f'packed staging: scene {b} filled out of order')
+                vals = parts[2] if parts[2].size <= self.capacity[key] else parts[2][:0]      # no slot holds it: its words stay behind, and
+                _put(self.host[name, 'mask'], b * (n // 32), parts[0])                        # the admit refuses it (count and capacity)
+                _put(self.host[name, 'offs'], b * (-(-n // SPARSE_BLOCK) + 1), parts[1])
+                _put(self.host[name, 'vals'], base[-1], vals)
+                base.append(base[-1] + vals.size)
+                self.host[name, 'base'].numpy()[:b + 2] = base
+            else:
+                raw = np.ascontiguousarray(parts[0]).view(np.uint8)
+                self.host[name, 'raw'].numpy()[b * raw.size:(b + 1) * raw.size] = raw
+
+    def upload(self, count):
+        for name, key, e, kind, n in self.feats:
+            for part in {'bits': ('bits',), 'sparse': ('mask', 'offs', 'base', 'vals'), 'raw': ('raw',)}[kind]:
+                h = self.host[name, part]
+                if part == 'base':
+                    k = count + 1
+                elif part == 'vals':
+                    k = self._base[name][count]
+                else:
+                    k = (h.numel() // max(self.B, 1)) * count
+                _pieces(self.dev_bufs[name, part], h, k, self.chunk)
+
+    def upload_bytes(self, count):
+        """Bytes upload(count) moves, as the pinned side stands."""
+        total = 0
+        for name, key, e, kind, n in self.feats:
+            for part in {'bits': ('bits',), 'sparse': ('mask', 'offs', 'base', 'vals'), 'raw': ('raw',)}[kind]:
+                h = self.host[name, part]
+                k = count + 1 if part == 'base' else self._base[name][count] if part == 'vals' else (h.numel() // max(self.B, 1)) * count
+                total += k * h.element_size()
+        return total
+
+    def launch(self, slots, count, ok):
+        """slots, ok: device pointers (int32 [count]).  Every admit runs before any put, so ok is final before the pool is written."""
+        N, st, arrs, d = self.pool.N, _st(), self.pool.dev_arrays, self.dev_bufs
+        sparse = [f for f in self.feats if f[3] == 'sparse']
+        for i, (name, key, e, _, n) in enumerate(sparse):
+            call('stj_pool_admit_packed', _p(d[name, 'offs']), -(-n // SPARSE_BLOCK), n, _p(d[name, 'base']), _p(arrs[key]['val_base']), slots, N, ok,
+                 count, int(i == 0), st)
+        if not sparse:
+            call('stj_pool_admit', None, 0, None, slots, N, ok, count, 1, st)
+        for name, key, e, kind, n in self.feats:
+            a = arrs[key]
+            if kind == 'bits':
+                call('stj_pool_put_raw', _p(d[name, 'bits']), 4, ok, slots, N, _p(a['words']), count, n // 32, st)
+            elif kind == 'sparse':
+                call('stj_pool_put_raw', _p(d[name, 'mask']), 4, ok, slots, N, _p(a['mask']), count, n // 32, st)
+                call('stj_pool_put_raw', _p(d[name, 'offs']), 4, ok, slots, N, _p(a['offs']), count, -(-n // SPARSE_BLOCK) + 1, st)
+                call('stj_pool_put_vals', _p(d[name, 'vals']), _p(d[name, 'base']), ok, slots, N, _p(a['val_base']), _p(a['vals']),
+                     self.pool._n_vals(key), count, st)
+            else:
+                call('stj_pool_put_raw', _p(d[name, 'raw']), ITEMSIZE[e['dtype']], ok, slots, N, _p(a['data']), count, n, st)
+
+
+class _Group:
+    """One consumed group of a ShuffleWindow on its way round: its position in perm, the event behind the gathers that read it, and what
+    the worker reports back -- how many scenes it refilled and the event behind their puts."""
+    __slots__ = ('pos', 'after', 'ready', 'count', 'done')
+
+    def __init__(self, pos, after, ready):
+        self.pos, self.after, self.ready, self.count, self.done = pos, after, ready, 0, None
+
+
+class ShuffleWindow:
+    """The reference's `dataset.shuffle(N)` (train.py:381) with the buffer in HBM: a rolling window of N scenes over a source of any length,
+    every source scene visited exactly once, at the rate of a ResidentPool.
+
+        pool = ResidentPool.empty(N, 'cuda', grid, out, capacity={...})
+        window = pool.window(B, source, lag=4)          # source: an iterator of pack_example records (packed=False: of raw records)
+        window.start()                                  # fills the N slots with the first N scenes
+        idx = window.next_batch()                       # device int32 [B]: B live slots, drawn on the device
+        pool.gather_into(step.static, idx); window.release()       # or WindowFeed(step.static, window).land()
+
+    State: perm int32 [N] on the device (initially arange(N)) and the host integers tail, head, n_live.  The live slots are
+    perm[tail : tail + n_live), circular mod N; the free ones follow, the oldest consumed group first at head.  N % B == 0 and
+    N >= (lag + 1) * B.
+    Draw (stj_pool_draw): from random words u uint32 [B], for i = 0 .. B - 1: m = n_live - i, j = (u[i] * m) >> 32, p = (tail + i) % N,
+    q = (tail + i + j) % N, swap perm[p] and perm[q], idx[i] = perm[p]; then tail = (tail + B) % N, n_live -= B.  The multiply-shift picks
+    j with a bias of at most m / 2^32 per draw (no rejection sampling).  The B consumed slots are the group perm[old tail : old tail + B),
+    which never wraps and is not touched again until it is admitted.
+    Refill and admission: consumed groups are refilled in FIFO order with the next B scenes of the source, by a worker thread on a stream
+    of its own (uploads from two staging sets, stj_pool_admit_packed / stj_pool_put_raw / stj_pool_put_vals reading their slots from
+    perm on the device; the host never learns a slot number).  The group consumed at step t is admitted immediately before the draw of
+    step t + lag (head += B, n_live += B), never earlier even if its refill is done, and the draw waits for it if it is not -- so the
+    sequence of batches is a pure function of (N, B, lag, the u rows, the source order); a steady-state draw finds N - (lag - 1) * B
+    live scenes and leaves N - lag * B.  ShuffleWindow.reference states all of it in Python.
+    End of the source: consumed groups are no longer refilled, a last partial group of r < B scenes fills the first r slots of its group
+    and is admitted with head += r, and the window drains; drop_last=True leaves the final fewer-than-B scenes unvisited (as PoolSampler
+    does), drop_last=False returns them as a short last batch; then next_batch() raises StopIteration.
+    Records that cannot land: the worker validates every record and checks the sparse keys against the slot capacity before upload; a
+    malformed or oversized record is never uploaded, is logged in window.skipped as (source ordinal, reason), and the next record takes
+    its place.  A device-side ok == 0 can then only mean corrupt staging: it is counted in window.bad (device int32 [1]) and such a slot
+    KEEPS ITS OLD SCENE, which is then visited a second time.
+    Counters: consumed (scenes returned), stalls (draws that found their refill unfinished and waited), skipped, bad.  An exception in the
+    worker (the source's included) is re-raised by the next next_batch() / release() / close().  close() joins the worker and drains the
+    refill stream.  Not built: state_dict (resuming mid-epoch), coordination across ranks (each rank windows its own shard), capture of
+    the draw in a graph, any eviction policy but consumed-first FIFO."""
+
+    def __init__(self, pool, batch_size, source, packed=True, lag=4, seed=0, drop_last=True, chunk_bytes=3 << 19):
+        import collections
+        import queue
+        import threading
+        N, B, K = pool.N, int(batch_size), int(lag)
+        if B < 1 or K < 1 or N % B or N < (K + 1) * B:
+            raise ValueError(f'ShuffleWindow: N {N}, B {B}, lag {K}: N a multiple of B and at least (lag + 1) * B, lag >= 1 only')
+        self.pool, self.N, self.B, self.lag, self.packed, self.drop_last = pool, N, B, K, bool(packed), bool(drop_last)
+        self.dev = pool.dev
+        self.source = iter(source)
+        self.perm = torch.arange(N, dtype=torch.int32, device=self.dev)
+        self.idx = torch.zeros((B,), dtype=torch.int32, device=self.dev)
+        self.bad = torch.zeros((1,), dtype=torch.int32, device=self.dev)
+        self.gen = torch.Generator(device=self.dev).manual_seed(int(seed))
+        self.refill = torch.cuda.Stream(self.dev)
+        self.tail = self.head = self.n_live = 0
+        self.consumed = self.stalls = self.steps = 0
+        self.skipped = []
+        if self.packed:
+            self._sets = [_PackedStage(pool, B, chunk_bytes) for _ in range(2)]
+            self._ok = [torch.zeros((B,), dtype=torch.int32, device=self.dev) for _ in self._sets]
+            self._free = [None for _ in self._sets]           # the event behind the last upload from a set's pinned side
+            self._checker = self._sets[0]
+        else:
+            self._sets = [PoolWriter(pool, B, chunk_bytes) for _ in range(2)]
+            self._raw_feats = [(name, key, e, nbytes) for name, key, e, nbytes, _ in self._sets[0].features]
+            lay = pool.layout
+            self._capacity = {key: int(e['capacity']) if lay.device_only else int(np.diff(e['val_base']).min())
+                              for _, key, e, _ in self._raw_feats if e['kind'] == 'sparse'}
+        self._q, self._pending, self._open = queue.Queue(), collections.deque(), None
+        self._ordinal, self._dry, self._stop, self._err, self._done = 0, False, False, None, False
+        self._thread = threading.Thread(target=self._run, daemon=True)
+        self._started = False
+
+    # ---- the NumPy / Python statement
+    @staticmethod
+    def reference(N, B, lag, u_rows, M, drop_last=True, live=None):
+        """The batches of a window of N slots, batch size B and lag `lag` over a source of M scenes, as lists of source ordinals; u_rows[t]
+        holds the random words of draw t.  live: a list that receives the live count every draw saw."""
+        N, B, K, M = int(N), int(B), int(lag), int(M)
+        if B < 1 or K < 1 or N % B or N < (K + 1) * B:
+            raise ValueError(f'ShuffleWindow.reference: N {N}, B {B}, lag {K}')
+        perm, holds = list(range(N)), [None] * N
+        n_live = min(N, M)
+        for s in range(n_live):                               # start(): group g takes scenes g * B ..
+            holds[s] = s
+        nxt, tail, head = n_live, 0, n_live % N
+        pending, batches, t = [], [], 0
+        while True:
+            if len(pending) == K:                             # the group consumed at step t - K
+                r = pending.pop(0)
+                head, n_live = (head + r) % N, n_live + r
+            b = B if n_live >= B else (0 if drop_last else n_live)
+            if b == 0:
+                return batches
+            if live is not None:
+                live.append(n_live)
+            u = [int(x) & 0xffffffff for x in u_rows[t]]
+            out = []
+            for i in range(b):
+                m = n_live - i
+                j = (u[i] * m) >> 32
+                p, q = (tail + i) % N, (tail + i + j) % N
+                perm[p], perm[q] = perm[q], perm[p]
+                out.append(holds[perm[p]])
+            batches.append(out)
+            if b < B:
+                return batches
+            r = min(B, M - nxt)                               # the refill: FIFO, the next r scenes into the group's first r slots
+            for i in range(r):
+                holds[perm[(tail + i) % N]] = nxt + i
+            nxt += r
+            pending.append(r)
+            tail, n_live, t = (tail + B) % N, n_live - B, t + 1
+
+    @staticmethod
+    def draw_reference(perm, tail, n_live, u):
+        """One draw as stj_pool_draw makes it, in NumPy: perm int32 [N] is permuted in place, -> idx int32 [len(u)].  As in the kernel every
+        position is taken mod N and a value read from perm is clamped to [0, N - 1] on its way into idx (perm itself keeps it)."""
+        N = perm.size
+        idx = np.zeros(len(u), np.int32)
+        for i, w in enumerate(u):
+            j = (int(w) * (int(n_live) - i)) >> 32
+            p, q = (tail + i) % N, (tail + i + j) % N
+            perm[p], perm[q] = perm[q], perm[p]
+            idx[i] = min(max(int(perm[p]), 0), N - 1)
+        return idx
+
+    # ---- the worker
+    def _validate(self, ex):
+        if self.packed:
+            parsed = self._checker.check(ex, 0)
+            why = self._checker.misfit(parsed)
+            if why is not None:
+                raise ValueError(why)
+            return parsed
+        grid, out, test, _ = self.pool.layout.geometry
+        spec = feature_spec(grid, out, test)
+        for name, key, e, nbytes in self._raw_feats:
+            if name not in ex or len(ex[name]) != nbytes:
+                raise ValueError(f"feature {name}: {len(ex[name]) if name in ex else 'no'} bytes, expected {nbytes}")
+            if e['kind'] == 'sparse':
+                dtype, shape, crop, _ = spec[name]
+                count = int(np.count_nonzero(_decoded(ex[name], dtype, shape, crop)))
+                if count > self._capacity[key]:
+                    raise ValueError(f'{key}: {count} value words, a slot holds {self._capacity[key]}')
+        return ex
+
+    def _pull(self):
+        """The next B records of the source that can land (fewer at its end); the others go to window.skipped."""
+        recs = []
+        while len(recs) < self.B and not self._dry:
+            try:
+                ex = next(self.source)
+            except StopIteration:
+                self._dry = True
+                break
+            ordinal, self._ordinal = self._ordinal, self._ordinal + 1
+            try:
+                recs.append(self._validate(ex))
+            except ValueError as e:
+                self.skipped.append((ordinal, str(e)))
+        return recs
+
+    def _prepare(self, k):
+        recs = self._pull()
+        if self.packed and recs:
+            if self._free[k] is not None:
+                self._free[k].synchronize()                   # the set's previous upload has left its pinned side
+            st = self._sets[k]
+            st.begin()
+            for b, p in enumerate(recs):
+                st.fill(b, p)
+        return recs
+
+    def _commit(self, g, k, recs):
+        r, B = len(recs), self.B
+        g.count = r
+        if not r:
+            return
+        with torch.cuda.stream(self.refill):
+            slots = self.perm[g.pos:g.pos + r]
+            if self.packed:
+                st, ok = self._sets[k], self._ok[k]
+                st.upload(r)
+                self._free[k] = torch.cuda.Event()
+                self._free[k].record(self.refill)
+                if g.after is not None:
+                    self.refill.wait_event(g.after)           # the gathers that read these slots are done
+                st.launch(_p(slots), r, _p(ok))
+            else:
+                w = self._sets[k]
+                ok = w.ok
+                w.stage(recs + [recs[-1]] * (B - r))
+                if g.after is not None:
+                    self.refill.wait_event(g.after)
+                w.slots[:r].copy_(slots, non_blocking=True)
+                if r < B:
+                    w.slots[r:].fill_(-1)                     # rows behind the source's end: skipped by every kernel
+                w.commit()
+            self.bad.add_(r - ok[:r].sum(dtype=torch.int32))
+            g.done = torch.cuda.Event()
+            g.done.record(self.refill)
+
+    def _run(self):
+        g = None
+        try:
+            torch.cuda.set_device(self.perm.device)           # a tensor's device carries its index
+            k, recs = 0, None
+            while True:
+                if recs is None:
+                    recs = self._prepare(k)
+                g = self._q.get()
+                if g is None:
+                    return
+                self._commit(g, k, recs)
+                g.ready.set()
+                g, recs, k = None, None, (k + 1) % len(self._sets)
+        except BaseException as e:                            # surfaced by the next next_batch() / release() / close()
+            self._err = e
+            while True:                                       # nobody waits for a group for ever
+                if g is not None:
+                    g.ready.set()
+                g = self._q.get()
+                if g is None:
+                    return
+
+    def _check(self):
+        if self._err is not None:
+            e, self._err = self._err, None
+            self._done = True
+            raise e
+
+    def _send(self, pos, after):
+        import threading
+        g = _Group(pos, after, threading.Event())
+        self._q.put(g)
+        return g
+
+    # ---- the training thread
+    def start(self):
+        """Fills the N slots with the first N scenes of the source (group g takes scenes g * B ..) and returns when they are there."""
+        if self._started:
+            raise RuntimeError('ShuffleWindow: started twice')
+        self._started = True
+        self.pool.wait()
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.dev))
+        self.refill.wait_event(ev)                            # perm and the pool's arrays exist
+        self._thread.start()
+        groups = [self._send(pos, None) for pos in range(0, self.N, self.B)]
+        for g in groups:
+            g.ready.wait()
+            self._check()
+        self.refill.synchronize()
+        self.n_live = sum(g.count for g in groups)
+        self.tail, self.head = 0, self.n_live % self.N
+        return self
+
+    def release(self):
+        """Call after the gathers of the last next_batch(): records the event behind them on the current stream and hands the consumed
+        group to the worker.  The next next_batch() does it if nobody has."""
+        if self._open is None:
+            return
+        pos, self._open = self._open, None
+        self._check()
+        after = torch.cuda.Event()
+        after.record(torch.cuda.current_stream(self.dev))
+        self._pending.append(self._send(pos, after))
+
+    def next_batch(self, u=None):
+        """-> device int32 [B] (the window's persistent idx; a short last batch is a view of it): the slots of the next batch.  u: B random
+        words (uint32, host) for a reproducible draw; None draws them on the device from the window's generator, with no host sync."""
+        if not self._started:
+            raise RuntimeError('ShuffleWindow: start() first')
+        self.release()
+        self._check()
+        if self._done:
+            raise StopIteration
+        main = torch.cuda.current_stream(self.dev)
+        if len(self._pending) == self.lag:                    # the group consumed lag steps ago
+            g = self._pending.popleft()
+            late = not g.ready.is_set()
+            g.ready.wait()
+            self._check()
+            if g.count:
+                if late or not g.done.query():
+                    late = True
+                    g.done.synchronize()
+                main.wait_event(g.done)
+                self.head, self.n_live = (self.head + g.count) % self.N, self.n_live + g.count
+            self.stalls += int(late)
+        b = self.B if self.n_live >= self.B else (0 if self.drop_last else self.n_live)
+        if b == 0:
+            self._done = True
+            raise StopIteration
+        if u is None:
+            words = (torch.randint(0, 1 << 32, (b,), dtype=torch.int64, device=self.dev, generator=self.gen) - (1 << 31)).to(torch.int32)
+        else:
+            host = np.asarray(u, dtype=np.uint64).reshape(-1)
+            if host.size < b or (host >> 32).any():
+                raise ValueError(f'ShuffleWindow: u must hold {b} 32-bit words')
+            words = torch.from_numpy((host[:b] & 0xffffffff).astype(np.uint32).view(np.int32)).to(self.dev)
+        call('stj_pool_draw', _p(self.perm), self.N, self.tail, self.n_live, _p(words), _p(self.idx), b, _st())
+        self._words = words                                   # alive until the stream has read it
+        self.consumed += b
+        self.steps += 1
+        if b == self.B:
+            self._open = self.tail
+        else:
+            self._done = True
+        self.tail, self.n_live = (self.tail + b) % self.N, self.n_live - b
+        return self.idx[:b]
+
+    def __iter__(self):
+        return self
+
+    __next__ = next_batch
+
+    def close(self):
+        """Joins the worker, drains the refill stream and re-raises what the worker died of, if anything."""
+        if self._thread.is_alive():
+            self._stop = True
+            self._q.put(None)
+            self._thread.join()
+        self.refill.synchronize()
+        self._done = True
+        self._check()
+
+
+class WindowFeed:
+    """HostFeed's protocol (start / land / wait_uploaded / close) over a ShuffleWindow, like ResidentFeed over a pool:
+
+        feed = WindowFeed(step.static, pool.window(B, source))
+        feed.start()
+        for ...:
+            feed.land()                    # draw, the pool's gathers into static, release; StopIteration when the source is used up
+            step(); optimizer.step()
+
+    land() draws into the persistent feed.idx (the window's), launches the gathers that read it and records the event that lets the
+    worker refill the consumed slots.  The landing stays in front of a captured step's replay; nothing of the window is captured."""
+
+    def __init__(self, static, window):
+        self.static, self.window, self.pool = static, window, window.pool
+        if not [k for k in self.pool.layout.entries if k in static]:
+            raise ValueError('WindowFeed: the pool holds none of the keys of `static`')
+        self.B, self.idx = window.B, window.idx
+        self.pool.check_static(static, self.B)
+
+    def start(self):
+        if not self.window._started:
+            self.window.start()
+
+    def land(self, u=None):
+        idx = self.window.next_batch(u)
+        if idx.numel() != self.B:
+            self.window.release()
+            raise ValueError(f'WindowFeed: a last batch of {idx.numel()} scenes for a static batch of {self.B} (drop_last=True avoids it)')
+        self.pool.gather_into(self.static, self.idx)
+        self.window.release()
+
+    def wait_uploaded(self):
+        return
+
+    def close(self):
+        self.window.close()

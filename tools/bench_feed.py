@@ -9,7 +9,9 @@ tensors), `raw` (HostFeed, the record's own bytes: bool grids and the int8 map o
 (PackedFeed: bool grids one bit per element, flows as mask + non-zero words, int8 map), `pool` (ResidentFeed, DESIGN 4u: --pool-scenes x B
 blob scenes packed the same way stay in HBM, every step gathers a freshly sampled batch by device index, nothing is uploaded), `replace`
 (opt-in through --modes: the same pool built by ResidentPool.empty and filled by a PoolWriter from raw records; every
---replace-every steps one put() of B raw records replaces B slots in front of the landing).  Per visit
+--replace-every steps one put() of B raw records replaces B slots in front of the landing), `window` / `window-raw` (opt-in
+through --modes: WindowFeed over a ShuffleWindow of --pool-scenes x B slots whose source cycles over the same records, packed by
+pack_example / raw; consumed slots are refilled by the window's worker on its own stream; `window@K` sets the lag, --lag the default).  Per visit
 every mode is timed TWICE in a row,
 the modes alternating, --pairs visits: the spread of repeated runs of one mode is measured in the same call.  One JSON line per run:
 scenes/s, bytes uploaded per scene, the density of the synthetic scene.
@@ -50,6 +52,7 @@ ap.add_argument('--trace', action='store_true')
 ap.add_argument('--trace-replace', action='store_true')
 ap.add_argument('--replace-put', action='store_true')
 ap.add_argument('--replace-every', type=int, default=8, help='mode replace: one put of B records every this many steps')
+ap.add_argument('--lag', type=int, default=4, help='modes window / window-raw: steps between the draw of a group and its admission')
 ap.add_argument('--put-grid', type=int, default=512)
 ap.add_argument('--put-out', type=int, default=256)
 ap.add_argument('--put-reps', type=int, default=10)
@@ -71,7 +74,7 @@ if a.all:
     for cfg in ('train', 'infer'):
         cmd = ['timeout', '-k', '10', str(a.timeout), sys.executable, os.path.abspath(__file__), '--config', cfg, '--modes', a.modes,
                '--steps', str(a.steps), '--warmup', str(a.warmup), '--pairs', str(a.pairs), '--blobs', str(a.blobs), '--seed', str(a.seed),
-               '--pool-scenes', str(a.pool_scenes), '--replace-every', str(a.replace_every)]
+               '--pool-scenes', str(a.pool_scenes), '--replace-every', str(a.replace_every), '--lag', str(a.lag)]
         if a.out:
             cmd += ['--out', a.out]
         r = subprocess.run(cmd)
@@ -84,7 +87,7 @@ import numpy as np
 import torch
 
 import bench
-from strajnet_amd.data import (POOL_NAMES, HostFeed, PackedFeed, PoolLayout, ResidentFeed, ResidentPool, SparseHost, bits_host,
+from strajnet_amd.data import (POOL_NAMES, HostFeed, PackedFeed, PoolLayout, ResidentFeed, ResidentPool, SparseHost, WindowFeed, bits_host,
                                feature_spec, pack_bits, pack_example, pack_sparse)
 
 assert torch.cuda.is_available(), 'bench_feed.py needs a GPU'
@@ -262,6 +265,28 @@ def make_replace_feed(static):
     return feed, sum(len(v) for v in batches[0][0].values()) * B / feed.every
 
 
+_WINDOW_RECORDS = {}
+
+
+def make_window_feed(static, mode):
+    """-> (WindowFeed over a ShuffleWindow of --pool-scenes x B slots, bytes uploaded per batch).  mode: window[-raw][@lag]; the source
+    cycles for ever over --pool-scenes x B blob records, already parsed (and, for `window`, already packed): what a loader thread hands
+    over.  The window's worker validates every record again on each pass."""
+    import itertools
+    kind, _, lag = mode.partition('@')
+    packed, lag = kind == 'window', int(lag or a.lag)
+    if 'raw' not in _WINDOW_RECORDS:
+        batches = [blob_records(B, a.seed + 1 + j, a.blobs) for j in range(a.pool_scenes)]
+        _WINDOW_RECORDS['capacity'] = record_capacity(batches, 256, 256)
+        _WINDOW_RECORDS['raw'] = [r for recs in batches for r in recs]
+    if packed and 'packed' not in _WINDOW_RECORDS:
+        _WINDOW_RECORDS['packed'] = [pack_example(r, 256, 256) for r in _WINDOW_RECORDS['raw']]
+    recs = _WINDOW_RECORDS['packed' if packed else 'raw']
+    pool = ResidentPool.empty(a.pool_scenes * B, dev, 256, 256, capacity=_WINDOW_RECORDS['capacity'])
+    feed = WindowFeed(static, pool.window(B, itertools.cycle(recs), packed=packed, lag=lag, seed=a.seed))
+    return feed, sum(len(v) for r in recs for v in r.values()) * B / len(recs)
+
+
 def writer_bytes(writer):
     """Per key: the kernels of one commit and the bytes they read and write (the source is read twice for a sparse key: count + commit)."""
     per = {}
@@ -413,7 +438,7 @@ modes = a.modes.split(',')
 feeds = {}
 for m in modes:
     feeds[m] = ((None, 0) if m == 'resident' else make_pool_feed(graphed.static) if m == 'pool' else make_replace_feed(graphed.static)
-                if m == 'replace' else make_feed(m, graphed.static, xh))
+                if m == 'replace' else make_window_feed(graphed.static, m) if m.startswith('window') else make_feed(m, graphed.static, xh))
     if feeds[m][0] is not None:
         feeds[m][0].start()
 for visit in range(a.pairs):
@@ -424,7 +449,10 @@ for visit in range(a.pairs):
             emit({'config': a.config, 'mode': m, 'visit': visit, 'rep': rep, 'batch': B, 'steps': a.steps, 'warmup': a.warmup,
                   'scenes_per_s': round(B * a.steps / dt, 1), 'ms_per_step': round(dt / a.steps * 1e3, 4),
                   'upload_bytes_per_scene': round(nbytes / B), 'blobs': a.blobs, 'density': density,
-                  **({'pool_scenes': feed.pool.N, 'pool_bytes_per_scene': round(feed.pool.nbytes / feed.pool.N)} if m in ('pool', 'replace') else {}),
+                  **({'pool_scenes': feed.pool.N, 'pool_bytes_per_scene': round(feed.pool.nbytes / feed.pool.N)}
+                     if m in ('pool', 'replace') or m.startswith('window') else {}),
+                  **({'lag': feed.window.lag, 'draws': feed.window.steps, 'stalls': feed.window.stalls, 'skipped': len(feed.window.skipped),
+                      'bad': int(feed.window.bad.item())} if m.startswith('window') else {}),
                   **({'replace_every': feed.every, 'puts': feed.puts} if m == 'replace' else {})})
 for feed, _ in feeds.values():
     if feed is not None:
