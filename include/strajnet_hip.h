@@ -671,6 +671,37 @@ int stj_eval_fwd(const float* logits, const float* gt_obs, const float* gt_occ, 
                  void* workspace, float* loss, float* metrics, float* gate, float* auc, double* running, int B, int H, int W,
                  float ogm_w, float occ_w, float flow_origin_w, float replica, float loss_scale, int flags, hipStream_t stream);
 
+/* Every scene of a validation batch scored ON ITS OWN, from one pass over the same inputs as stj_eval_fwd (same flags, weights and
+ * replica); stj_eval_fwd itself is unchanged.  Nothing is pooled across scenes and there is no floating-point atomic.
+ * rows f32[B][12]: per scene observed_xe, occluded_xe, flow, flow_warp_xe, their sum, then the seven metrics -- what OGMFlow_loss and
+ * the metrics give for that scene as a batch of one.  A row depends on its scene alone: the same scene gives the same bits alone, in a
+ * batch of any size and at any position (stj_eval_scenes_grid(H, W) workgroups per scene, a function of the shape only; partial sums
+ * added in a fixed order).  A scene without vehicle occupancy has every gate 0 under use_gt: its flow, flow_warp_xe and sum are NaN (the
+ * reference divides 0 by 0, loss.py:164,167), the other columns finite.  gate f32[B][8] and auc f32[B][8][4] per scene, optional.
+ * live: optional device int32[B] (NULL: every scene is live).  A scene with live[b] == 0 is not scored, none of its inputs is read;
+ * its row, gate and auc are written as zeros and it enters neither state, table nor the pooled result.
+ * batch_loss f32[5], batch_metrics f32[7], batch_gate f32[8], batch_auc f32[32]: optional, the POOLED result of the live scenes =
+ * what stj_eval_fwd computes for the sub-batch of the live scenes: gate and auc equal to it (the pooled histograms are the integer
+ * sums of the scenes'), the float sums folded in double scene by scene, so loss and metrics differ from it in summation order only.
+ * Without a live scene all four are written as zeros.
+ * state: optional device double[2][13], added to by the last launch, live scenes in batch order: [0][c] the sum and [1][c] the count
+ * of column c of the rows (the five loss columns x loss_scale); a NON-FINITE value is added to neither (unlike Keras Mean: one empty
+ * scene must not turn an epoch's mean into NaN); [0][12] = scenes scored, [1][12] = scenes with at least one non-finite column.
+ * table f32[capacity][12] with cursor (device long long[1]): live rows are appended in batch order at *cursor, which advances by the
+ * number of live scenes even when the table is full; rows at or beyond capacity are dropped, nothing is stored outside the table.
+ * A cursor without a table only counts.
+ * workspace: stj_eval_scenes_workspace_bytes(B, H, W) bytes, 16-byte aligned, ANY contents on entry.  Five launches on `stream` (four
+ * without state, cursor and pooled outputs), no allocation, no host synchronisation.  STJ_EINVAL before any launch, nothing written:
+ * logits not 16-byte, gt_flow / state / cursor not 8-byte, workspace not 16-byte aligned; unknown flag bits; capacity < 0; a table
+ * without a cursor; B > 65534.  B*H*W <= 0: nothing is launched or written. */
+long long stj_eval_scenes_workspace_bytes(int B, int H, int W);
+int stj_eval_scenes_grid(int H, int W);
+int stj_eval_scenes_fwd(const float* logits, const float* gt_obs, const float* gt_occ, const float* gt_flow, const float* origin,
+                        const int* live, void* workspace, float* rows, float* gate, float* auc, float* batch_loss, float* batch_metrics,
+                        float* batch_gate, float* batch_auc, double* state, float* table, long long* cursor, long long capacity,
+                        int B, int H, int W, float ogm_w, float occ_w, float flow_origin_w, float replica, float loss_scale,
+                        int flags, hipStream_t stream);
+
 /* Training-time randomness.  Keras Dropout / tfa-MHA attention dropout (trajNet.py:33,71,75,77,195,209,211) and DropPath
  * (modules.py:137-151) share one rule: y = [res +] keep(draw) * x / (1 - p), keep = U[0,1) >= p, draw(i) = i / inner
  * (inner = 1: per element; inner = elements per sample: DropPath with p = drop_prob).  U comes from Philox-4x32-10 keyed by

@@ -10,7 +10,7 @@ from .loss import (OGMFlow_loss, WaypointGrids, OccupancyFlowTaskConfig,     # n
 from .optim import Nadam, DeviceNadam, CosineDecayRestarts, CustomSchedule     # noqa: F401
 from .training import train_step     # noqa: F401
 from .metrics import compute_occupancy_flow_metrics, apply_sigmoid_to_occupancy_logits, OccupancyFlowMetrics     # noqa: F401
-from .evaluate import Mean, OGMFlowMetrics, print_metrics, eval_step     # noqa: F401
+from .evaluate import Mean, OGMFlowMetrics, SceneScores, print_metrics, eval_step     # noqa: F401
 from .submission import (QuantizedWaypoints, ResultDrain, quantize_waypoints, quantize_reference,     # noqa: F401
                          compress_batch, compression_pool, CompressedWaypoints, compress_waypoints, compress_reference,
                          DEFLATE_SEGMENT)

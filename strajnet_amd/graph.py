@@ -264,19 +264,27 @@ class GraphedEvalStep:
 
     __call__(batch=None) loads the batch and replays; .logits / .losses / .metrics are static device tensors ([B,H,W,32] f32, the
     four loss terms, the seven metrics in the order of metrics.FIELDS), .result() the means since the last reset() as a dict
-    (one host sync): the four losses x loss_fn.replica under the names of evaluate.LOSS_KEYS, the metrics under evaluate.METRIC_KEYS."""
+    (one host sync): the four losses x loss_fn.replica under the names of evaluate.LOSS_KEYS, the metrics under evaluate.METRIC_KEYS.
+
+    per_scene=True, capacity=N captures the per-scene pass (stj_eval_scenes_fwd) instead: .scores is an evaluate.SceneScores of N rows,
+    .scene_rows the static [B,12] rows of the last replay, .live a static device int32[B].  __call__(batch, live=None) then accepts a
+    batch of k <= B scenes (live = k, or the batch's own length): the first k static slots are loaded, live = [1] * k + [0] * (B - k) is
+    copied in front of the replay, and the stale tail is never read by the pass.  .losses / .metrics / .result() are the pooled numbers
+    of the live scenes: a last short batch is pooled over its real scenes only.  Without per_scene nothing changes."""
 
     KEYS = ('ogm', 'map_img', 'obs', 'occ', 'flow', 'gt_obs', 'gt_occ', 'gt_flow', 'origin_flow')
 
-    def __init__(self, model, loss_fn, batch, warmup=2, no_warp=False):
+    def __init__(self, model, loss_fn, batch, warmup=2, no_warp=False, per_scene=False, capacity=0):
         from .evaluate import eval_loss_metrics
         self._pass = eval_loss_metrics
-        self.model, self.loss_fn, self.no_warp = model, loss_fn, no_warp
+        self.model, self.loss_fn, self.no_warp, self.per_scene = model, loss_fn, no_warp, per_scene
         self.static = {k: v.clone() for k, v in batch.items() if k in self.KEYS}
         dev = self.static['ogm'].device
         self.running = torch.zeros(12, dtype=torch.float64, device=dev)      # count, 4 losses x replica, 7 metrics
         B, H, W = self.static['gt_obs'].shape[0], self.static['gt_obs'].shape[2], self.static['gt_obs'].shape[3]
-        self._ws = ops.eval_workspace(B, H, W, dev)
+        self._ws = ops.eval_workspace(B, H, W, dev) if not per_scene else ops.eval_scenes_workspace(B, H, W, dev)
+        if per_scene:
+            self._scene_state(B, capacity, dev)
         side = ops.role_stream(torch.cuda.current_device(), 'warmup')
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.no_grad():
@@ -285,14 +293,39 @@ class GraphedEvalStep:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.running.zero_()                 # the warm-up steps are not part of any mean
+        if per_scene:
+            self.scores.reset()
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.no_grad(), torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
             self.logits, self.losses, self.metrics = self._eager()
 
+    def _scene_state(self, B, capacity, dev):
+        from .evaluate import SceneScores
+        self.scores = SceneScores(capacity, no_warp=self.no_warp, device=dev)
+        self.live = torch.ones(B, dtype=torch.int32, device=dev)
+        self.scene_rows = torch.zeros(B, 12, dtype=torch.float32, device=dev)
+        # the pooled losses[5] and metrics[7] of a replay, then a constant 1: gathered and scaled into `running`'s layout by two launches
+        self._pooled = torch.zeros(13, dtype=torch.float32, device=dev)
+        self._pooled[12] = 1.0
+        self._pick = torch.tensor([12, 0, 1, 2, 3, 5, 6, 7, 8, 9, 10, 11], device=dev)
+        r = float(self.loss_fn.replica)
+        self._scale = torch.tensor([1.0] + [r] * 4 + [1.0] * 7, dtype=torch.float64, device=dev)
+
+    def _eager_scenes(self, out):
+        from .evaluate import eval_scene_loss_metrics
+        x = self.static
+        d, m = eval_scene_loss_metrics(self.loss_fn, get_pred_waypoint_logits(out),
+                                       warpped_gt(x['gt_obs'], x['gt_occ'], x['gt_flow'], x['origin_flow']), self.scores, live=self.live,
+                                       no_warp=self.no_warp, workspace=self._ws, rows=self.scene_rows, pooled_out=self._pooled[:12])
+        self.running.addcmul_(self._pooled[self._pick].double(), self._scale)       # count, 4 losses x replica, 7 metrics
+        return out, d.packed, m.values
+
     def _eager(self):
         x = self.static
         out = self.model(x['ogm'], x['map_img'], training=False, obs=x['obs'], occ=x['occ'], mapt=None, flow=x['flow'])
+        if self.per_scene:
+            return self._eager_scenes(out)
         d, m = self._pass(self.loss_fn, get_pred_waypoint_logits(out), warpped_gt(x['gt_obs'], x['gt_occ'], x['gt_flow'], x['origin_flow']),
                           no_warp=self.no_warp, running=self.running, workspace=self._ws)
         return out, d.packed, m.values
@@ -303,8 +336,27 @@ class GraphedEvalStep:
             if k in self.static:
                 self.static[k].copy_(v, non_blocking=True)
 
-    def __call__(self, batch=None):
+    def load_scenes(self, batch, live=None):
+        """A batch of k <= B scenes into the first k static slots, live = [1] * k + [0] * (B - k); the tail keeps what it held."""
+        B = self.live.numel()
+        k = B
         if batch is not None:
+            k = min(int(v.shape[0]) for key, v in batch.items() if key in self.static and v is not None)
+            for key, v in batch.items():
+                if key in self.static and v is not None:
+                    self.static[key][:k].copy_(v[:k], non_blocking=True)
+        if live is not None:
+            k = int(live)
+        if not 0 <= k <= B:
+            raise ValueError(f'live = {k} scenes in a step captured for {B}')
+        self.live.copy_((torch.arange(B, device=self.live.device) < k).to(torch.int32), non_blocking=True)
+
+    def __call__(self, batch=None, live=None):
+        if self.per_scene:
+            self.load_scenes(batch, live)
+        elif live is not None:
+            raise ValueError('GraphedEvalStep: live needs per_scene=True')
+        elif batch is not None:
             self.load(batch)
         self.graph.replay()
         return self.losses, self.metrics
@@ -319,3 +371,5 @@ class GraphedEvalStep:
 
     def reset(self):
         self.running.zero_()
+        if self.per_scene:
+            self.scores.reset()

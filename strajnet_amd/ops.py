@@ -2622,3 +2622,72 @@ def eval_loss_metrics(logits, gt_obs, gt_occ, gt_flow, origin, ogm_w, occ_w, fow
     call('stj_eval_fwd', _p(logits), _p(gt_obs), _p(gt_occ), _p(gt_flow), _p(origin), _p(workspace), _p(loss), _p(met), _p(gate), _p(auc),
          _p(running), B, H, W, float(ogm_w), float(occ_w), float(fow), float(replica), float(loss_scale), int(flags), _st())
     return (loss, met, gate, auc) if with_gate else (loss, met)
+
+
+def eval_scenes_workspace_bytes(B, H, W):
+    from ._lib import lib
+    return int(lib().stj_eval_scenes_workspace_bytes(int(B), int(H), int(W)))
+
+
+def eval_scenes_workspace(B, H, W, device):
+    """Scratch of one stj_eval_scenes_fwd call (stj_eval_scenes_workspace_bytes): any contents, the entry clears what it needs itself."""
+    return torch.empty(eval_scenes_workspace_bytes(B, H, W), dtype=torch.uint8, device=device)
+
+
+def eval_scenes_grid(H, W):
+    """Workgroups per scene of the per-scene pass: a function of the shape alone (csrc/eval_scene.h, evs_grid)."""
+    from ._lib import lib
+    return int(lib().stj_eval_scenes_grid(int(H), int(W)))
+
+
+def eval_scene_scores(logits, gt_obs, gt_occ, gt_flow, origin, ogm_w, occ_w, fow, replica, flags, live=None, state=None, table=None,
+                      cursor=None, loss_scale=1.0, workspace=None, pooled=True, with_gate=False, rows=None, pooled_out=None):
+    """Every scene of the batch scored on its own from one pass over the logits [B,H,W,32] and the ground truth (stj_eval_scenes_fwd;
+    forward only) -> dict: rows f32[B,12] (the four loss terms, their sum, the seven metrics in the order of metrics.FIELDS; zeros for a
+    dead scene) [, loss f32[5], metrics f32[7]: the pooled result of the live scenes = stj_eval_fwd on that sub-batch]
+    [, gate f32[B,8], auc f32[B,8,4], batch_gate f32[8], batch_auc f32[8,4]].  flags as eval_loss_metrics.
+    live: int32[B] on the device (None: every scene); state: f64[2,13]; table: f32[capacity,12] with cursor: int64[1] -- the
+    live rows are added to the state and appended at the cursor on the device (evaluate.SceneScores owns the three).
+    rows / pooled_out (f32[B,12] / f32[12]): preallocated outputs (a captured step keeps them static)."""
+    _req_cuda(logits, gt_obs, gt_occ, gt_flow, origin, live, state, table, cursor, workspace, rows, pooled_out)
+    logits = logits.detach().contiguous().float()
+    gt_obs, gt_occ, gt_flow, origin = (t.detach().contiguous().float() for t in (gt_obs, gt_occ, gt_flow, origin))
+    B, H, W, C = logits.shape
+    if C != 32 or tuple(gt_obs.shape) != (B, 8, H, W, 1) or tuple(gt_occ.shape) != (B, 8, H, W, 1) or \
+            tuple(gt_flow.shape) != (B, 8, H, W, 2) or tuple(origin.shape) != (B, 8, H, W, 1):
+        raise ValueError('eval_scene_scores: logits must be [B,H,W,32] and the ground truth [B,8,H,W,{1,1,2,1}]')
+    if live is not None and (live.dtype != torch.int32 or live.numel() != B or not live.is_contiguous()):
+        raise ValueError('eval_scene_scores: live must be a contiguous int32 tensor of B elements')
+    if state is not None and (state.dtype != torch.float64 or state.numel() != 26 or not state.is_contiguous()):
+        raise ValueError('eval_scene_scores: state must be a contiguous float64 tensor [2,13]')
+    if cursor is not None and (cursor.dtype != torch.int64 or cursor.numel() != 1):
+        raise ValueError('eval_scene_scores: cursor must be an int64 tensor of one element')
+    if table is not None and (table.dtype != torch.float32 or table.dim() != 2 or table.shape[1] != 12 or not table.is_contiguous()
+                              or cursor is None):
+        raise ValueError('eval_scene_scores: table must be a contiguous float32 tensor [capacity,12] and comes with a cursor')
+    for t, n, what in ((rows, B * 12, 'rows'), (pooled_out, 12, 'pooled_out')):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous()):
+            raise ValueError(f'eval_scene_scores: {what} must be a contiguous float32 tensor of {n} elements')
+    dev = logits.device
+    if workspace is None:
+        workspace = eval_scenes_workspace(B, H, W, dev)
+    elif workspace.numel() * workspace.element_size() < eval_scenes_workspace_bytes(B, H, W):
+        raise ValueError('eval_scene_scores: the workspace is smaller than stj_eval_scenes_workspace_bytes')
+    f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    out = dict(rows=rows.view(B, 12) if rows is not None else f32(B, 12))
+    if pooled:
+        both = pooled_out if pooled_out is not None else f32(12)
+        out['loss'], out['metrics'] = both[:5], both[5:]
+    if with_gate:
+        out['gate'], out['auc'] = f32(B, 8), f32(B, 8, 4)
+        if pooled:
+            out['batch_gate'], out['batch_auc'] = f32(8), f32(8, 4)
+    if B * H * W == 0:           # the entry launches and writes nothing
+        for v in out.values():
+            v.zero_()
+    g = out.get
+    call('stj_eval_scenes_fwd', _p(logits), _p(gt_obs), _p(gt_occ), _p(gt_flow), _p(origin), _p(live), _p(workspace), _p(out['rows']),
+         _p(g('gate')), _p(g('auc')), _p(g('loss')), _p(g('metrics')), _p(g('batch_gate')), _p(g('batch_auc')), _p(state), _p(table),
+         _p(cursor), 0 if table is None else int(table.shape[0]), B, H, W, float(ogm_w), float(occ_w), float(fow), float(replica),
+         float(loss_scale), int(flags), _st())
+    return out
