@@ -27,6 +27,7 @@ A shuffle buffer in HBM over a stream of any length: `ShuffleWindow` (pool.windo
 stj_pool_put_raw / stj_pool_put_vals); `WindowFeed` has HostFeed's protocol, `PoolWriter.put_packed` is the synchronous form;
 `ShuffleWindow.reference` and `PoolLayout.replace_packed_reference` state the semantics.
 """
+import collections
 import ctypes
 import struct
 
@@ -383,6 +384,21 @@ def unpack_example_reference(packed, grid=512, out=256, test=False):
 
 
 # ---------------------------------------------------------------------------------------------------- device decode
+def _hip_device(who, device):
+    """torch.device(device); RuntimeError unless it is a GPU."""
+    dev = torch.device(device)
+    if dev.type != 'cuda':
+        raise RuntimeError(f'{who}: CUDA (ROCm) device only: the HIP path has no CPU fallback')
+    return dev
+
+
+def _with_scenario_ids(res, examples, test):
+    """'scenario/id' is not a tensor: the test records' ids ride along as a list of bytes."""
+    if test and 'scenario/id' in examples[0]:
+        res['scenario/id'] = [bytes(ex['scenario/id']) for ex in examples]
+    return res
+
+
 def _decode_raw_feature(examples, name, spec, dev):
     """One feature of a batch from the record's own bytes: pinned upload + stj_decode_raw (crop, cast, scale)."""
     dtype, shape, crop, scale = spec
@@ -411,13 +427,9 @@ def decode_batch(examples, device='cuda', grid=512, out=256, test=False):
     shaped and cropped as _parse_image_function does (train.py:87-103): ogm [B,g,g,11,2], map_image [B,o,o,3] (/256),
     vec_flow [B,g,g,2], actors [B,48,11,8], occl_actors [B,16,11,8], centerlines [B,256,10,7] and, unless test,
     gt_flow [B,8,o,o,2], origin_flow / gt_obs_ogm / gt_occ_ogm [B,8,o,o,1]."""
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise RuntimeError('decode_batch: CUDA (ROCm) device only: the HIP path has no CPU fallback')
+    dev = _hip_device('decode_batch', device)
     res = {name: _decode_raw_feature(examples, name, sp, dev) for name, sp in feature_spec(grid, out, test).items()}
-    if test and 'scenario/id' in examples[0]:
-        res['scenario/id'] = [bytes(ex['scenario/id']) for ex in examples]
-    return res
+    return _with_scenario_ids(res, examples, test)
 
 
 def _pinned_words(n):
@@ -447,9 +459,7 @@ def decode_batch_packed(examples, device='cuda', grid=512, out=256, test=False):
     """decode_batch for records written by pack_example: the same dict, shapes and float32 values, bit for bit.  The packed features
     cross PCIe as they are stored (a sparse plane: only its used words) and are expanded by stj_unpack_bits / stj_unpack_sparse; the
     unpacked ones go through stj_decode_raw as in decode_batch.  Every stream is checked on the host before any launch (ValueError)."""
-    dev = torch.device(device)
-    if dev.type != 'cuda':
-        raise RuntimeError('decode_batch_packed: CUDA (ROCm) device only: the HIP path has no CPU fallback')
+    dev = _hip_device('decode_batch_packed', device)
     B = len(examples)
     spec = feature_spec(grid, out, test)
     todo = []
@@ -492,9 +502,7 @@ def decode_batch_packed(examples, device='cuda', grid=512, out=256, test=False):
             d = [t.to(dev, non_blocking=True) for t in (mask, offs, vb, vals)]
             call('stj_unpack_sparse', _p(d[0]), _p(d[1]), _p(d[2]), _p(d[3]), total, _p(dst), B, n, _st())
         res[name] = dst
-    if test and 'scenario/id' in examples[0]:
-        res['scenario/id'] = [bytes(ex['scenario/id']) for ex in examples]
-    return res
+    return _with_scenario_ids(res, examples, test)
 
 
 # ---------------------------------------------------------------------------------------------------- per-step feed of a captured step
@@ -508,6 +516,15 @@ def _copy_stream(dev):
     if key not in _COPY_STREAMS:
         _COPY_STREAMS[key] = torch.cuda.Stream(dev)
     return _COPY_STREAMS[key]
+
+
+def _copy_chunked(dst, src, count, chunk_bytes):
+    """dst[:count] <- src[:count] (flat tensors, host to device) in copies of at most chunk_bytes, on the current stream.  The one
+    upload loop of this module: HostFeed explains the pieces."""
+    step = max(1, chunk_bytes // src.element_size())
+    for i in range(0, count, step):
+        j = min(count, i + step)
+        dst[i:j].copy_(src[i:j], non_blocking=True)
 
 
 class HostFeed:
@@ -541,7 +558,11 @@ class HostFeed:
         for k, h in self.host.items():
             if not h.is_pinned():
                 raise ValueError(f'HostFeed: host[{k!r}] must be pinned memory')
+        for k, kind in self.raw.items():
+            if k in self.host and kind not in ('bool', 'int8'):               # one byte per element: what land() hands stj_decode_raw
+                raise ValueError(f"HostFeed: raw[{k!r}] is {kind!r}, 'bool' or 'int8' only")
         self.stage = {k: torch.empty(h.shape, dtype=h.dtype, device=dev) for k, h in self.host.items()}
+        self._landing = self.stage                      # what land() expands, in launch order
         self.chunk = int(chunk_bytes)
         self.copy = _copy_stream(dev)
         self.up, self.landed = torch.cuda.Event(), torch.cuda.Event()
@@ -554,12 +575,12 @@ class HostFeed:
     def _upload(self):
         with torch.cuda.stream(self.copy):
             self.copy.wait_event(self.landed)            # the staging buffers are free once the previous batch has left them
-            for k, h in self.host.items():
-                hs, ss = h.view(-1), self.stage[k].view(-1)
-                step = max(1, self.chunk // h.element_size())
-                for i in range(0, hs.numel(), step):
-                    ss[i:i + step].copy_(hs[i:i + step], non_blocking=True)
+            self._copies()
             self.up.record(self.copy)
+
+    def _copies(self):
+        for k, h in self.host.items():
+            _copy_chunked(self.stage[k].view(-1), h.view(-1), h.numel(), self.chunk)
 
     def _run(self):
         torch.cuda.set_device(self.dev)
@@ -587,16 +608,18 @@ class HostFeed:
         self._check()
         main = torch.cuda.current_stream(self.dev)
         main.wait_event(self.up)
-        kind = {'bool': 0, 'int8': 1}
-        for k, st in self.stage.items():
-            dst = self.static[k]
-            if k in self.raw:
-                n = dst.numel()
-                call('stj_decode_raw', _p(st), kind[self.raw[k]], _p(dst), 1, 1, n, 1, 0, 0, 1, n, (1.0 / 256.0) if self.raw[k] == 'int8' else 1.0, _st())
-            else:
-                dst.copy_(st, non_blocking=True)
+        for k, st in self._landing.items():
+            self._expand(k, st, self.static[k])
         self.landed.record(main)
         self._go.set()                                       # next batch: whatever host[...] holds now
+
+    def _expand(self, k, st, dst):
+        """One staged key into its static tensor, on the current stream."""
+        if k in self.raw:
+            n = dst.numel()
+            call('stj_decode_raw', _p(st), KIND[self.raw[k]], _p(dst), 1, 1, n, 1, 0, 0, 1, n, (1.0 / 256.0) if self.raw[k] == 'int8' else 1.0, _st())
+        else:
+            dst.copy_(st, non_blocking=True)
 
     def wait_uploaded(self):
         """Host-side: returns once the upload kicked off by the last land() has left the host buffers (a loader may refill them)."""
@@ -689,46 +712,25 @@ class PackedFeed(HostFeed):
                     raise ValueError(f'PackedFeed: host[{k!r}].{part} must be pinned memory')
         self.sparse_stage = {k: {part: torch.empty(h.shape, dtype=h.dtype, device=self.dev) for part, h in sh.parts().items()}
                              for k, sh in self.sparse.items()}
+        self._landing = {**self.stage, **self.sparse_stage}                # the sparse keys land behind the others
 
-    def _pieces(self, hs, ss, n):
-        step = max(1, self.chunk // hs.element_size())
-        for i in range(0, n, step):
-            j = min(n, i + step)
-            ss[i:j].copy_(hs[i:j], non_blocking=True)
+    def _copies(self):
+        super()._copies()
+        for k, sh in self.sparse.items():
+            count = min(int(sh.count), sh.vals.numel())
+            self._n_vals[k] = count                                        # read by the land() of THIS batch, before the next upload starts
+            for part, h in sh.parts().items():
+                _copy_chunked(self.sparse_stage[k][part], h, count if part == 'vals' else h.numel(), self.chunk)
 
-    def _upload(self):
-        with torch.cuda.stream(self.copy):
-            self.copy.wait_event(self.landed)
-            for k, h in self.host.items():
-                self._pieces(h.view(-1), self.stage[k].view(-1), h.numel())
-            for k, sh in self.sparse.items():
-                count = min(int(sh.count), sh.vals.numel())
-                self._n_vals[k] = count                                    # read by the land() of THIS batch, before the next upload starts
-                for part, h in sh.parts().items():
-                    self._pieces(h, self.sparse_stage[k][part], count if part == 'vals' else h.numel())
-            self.up.record(self.copy)
-
-    def land(self):
-        self._enqueued.wait(); self._enqueued.clear()
-        self._check()
-        main = torch.cuda.current_stream(self.dev)
-        main.wait_event(self.up)
-        kind = {'bool': 0, 'int8': 1}
-        for k, st in self.stage.items():
-            dst = self.static[k]
-            n = dst.numel()
-            if self.packed.get(k) == 'bits':
-                call('stj_unpack_bits', _p(st), _p(dst), n, _st())
-            elif k in self.raw:
-                call('stj_decode_raw', _p(st), kind[self.raw[k]], _p(dst), 1, 1, n, 1, 0, 0, 1, n, (1.0 / 256.0) if self.raw[k] == 'int8' else 1.0, _st())
-            else:
-                dst.copy_(st, non_blocking=True)
-        for k, st in self.sparse_stage.items():
-            dst = self.static[k]
+    def _expand(self, k, st, dst):
+        kind = self.packed.get(k)
+        if kind == 'bits':
+            call('stj_unpack_bits', _p(st), _p(dst), dst.numel(), _st())
+        elif kind == 'sparse':
             B = dst.shape[0]
             call('stj_unpack_sparse', _p(st['mask']), _p(st['offs']), _p(st['val_base']), _p(st['vals']), self._n_vals[k], _p(dst), B, dst.numel() // B, _st())
-        self.landed.record(main)
-        self._go.set()
+        else:
+            super()._expand(k, st, dst)
 
     def upload_bytes(self):
         """Bytes the next upload moves, as the host buffers stand."""
@@ -747,18 +749,35 @@ def _scene_words(x):
     return None if b.size % 4 else b.view('<u4')
 
 
-def _packed_parts(ex, b, grid, out, test, names, entries):
-    """The arrays of ONE pack_example record as a pool's keys hold them: [(key, parts)] with parts (words,) for a bits key, check_sparse's
-    (mask, offs, vals) for a sparse key and (the record's own elements,) for a raw key.  ValueError naming key and scene `b` for a missing
-    or malformed feature, or a key whose kind or size is not the record's."""
-    res = []
+_Feature = collections.namedtuple('_Feature', 'name key entry kind n dtype shape crop scale')
+
+
+def _feature_table(geometry, entries=None):
+    """The record features of a geometry (grid, out, test, names) as a pool holds them, one _Feature per row of feature_spec: the record
+    name, the pool key, the key's entry in `entries`, the kind PACKED_KIND gives it ('bits' / 'sparse' / 'raw'), n elements per scene after
+    the centre crop, and feature_spec's dtype, shape, crop and scale.  With entries: ValueError naming the key unless its entry holds that
+    kind and n and, for a raw key, that dtype with no crop (stj_pool_put_raw copies whole rows; no row of feature_spec is raw and
+    cropped).  Without: entry is None and nothing is checked -- for the code that builds the entries."""
+    grid, out, test, names = geometry
     for name, (dtype, shape, crop, scale) in feature_spec(grid, out, test).items():
         key = names.get(name, name)
-        e = entries.get(key)
-        want = PACKED_KIND.get(name, 'raw')
+        kind = PACKED_KIND.get(name, 'raw')
         n = int(np.prod(decoded_shape(shape, crop)))
-        if e is None or e['kind'] != want or e['n'] != n or (want == 'raw' and e['dtype'] != dtype):
-            raise ValueError(f"PoolLayout[{key!r}]: holds {None if e is None else (e['kind'], e['n'])}, a packed record gives {want} scenes of {n} elements")
+        e = None
+        if entries is not None:
+            e = entries.get(key)
+            if e is None or e['kind'] != kind or e['n'] != n or (kind == 'raw' and (e['dtype'] != dtype or crop is not None)):
+                raise ValueError(f"PoolLayout[{key!r}]: holds {None if e is None else (e['kind'], e['n'], e.get('dtype'))}, the record feature "
+                                 f"{name} gives {(kind, n, dtype if kind == 'raw' else None)}")
+        yield _Feature(name, key, e, kind, n, dtype, shape, crop, scale)
+
+
+def _packed_parts(ex, b, table):
+    """The arrays of ONE pack_example record as a pool's keys hold them: [(key, parts)] with parts (words,) for a bits key, check_sparse's
+    (mask, offs, vals) for a sparse key and (the record's own elements,) for a raw key; table: the checked _feature_table of the pool.
+    ValueError naming key and scene `b` for a missing or malformed feature."""
+    res = []
+    for name, key, _, want, n, dtype, shape, crop, _ in table:
         try:
             if want == 'bits':
                 w = _scene_words(ex[name + '/bits'])
@@ -886,11 +905,8 @@ class PoolLayout:
         names = POOL_NAMES if names is None else names
         exs = list(packed_examples)
         self = cls()
-        for name, (dtype, shape, crop, scale) in feature_spec(grid, out, test).items():
-            key = names.get(name, name)
+        for name, key, _, kind, n, dtype, shape, crop, scale in _feature_table((grid, out, test, names)):
             dshape = decoded_shape(shape, crop)
-            n = int(np.prod(dshape))
-            kind = PACKED_KIND.get(name)
             try:
                 if kind == 'bits' and exs and name + '/bits' in exs[0]:
                     self.add_bits(key, [ex[name + '/bits'] for ex in exs], dshape)
@@ -920,11 +936,8 @@ class PoolLayout:
         if N < 1:
             raise ValueError(f'PoolLayout.empty: {N} scenes: an empty pool')
         plan = []
-        for name, (dtype, shape, crop, scale) in feature_spec(grid, out, test).items():
-            key = names.get(name, name)
+        for name, key, _, kind, n, dtype, shape, crop, scale in _feature_table((grid, out, test, names)):
             dshape = decoded_shape(shape, crop)
-            n = int(np.prod(dshape))
-            kind = PACKED_KIND.get(name, 'raw')
             if kind != 'raw' and n % 32:
                 raise ValueError(f'PoolLayout[{key!r}]: {n} elements per scene, a multiple of 32 only')
             if n >= 1 << 32:
@@ -967,49 +980,49 @@ class PoolLayout:
         written from val_base[s] on in element order (the slot's words behind them keep what they held); the raw rows -- and a scene that is
         not admitted changes no key of any slot.  -> [1 | 0] per scene.  Duplicate slots raise ValueError, and so does a record whose
         feature has the wrong length or a key whose kind is not the one `empty` gives it."""
-        names = POOL_NAMES if names is None else names
-        slots = [int(s) for s in slots]
-        examples = list(examples)
-        if len(slots) != len(examples):
-            raise ValueError(f'replace_reference: {len(slots)} slots for {len(examples)} scenes')
-        if len(set(slots)) != len(slots):
-            raise ValueError(f'replace_reference: duplicate slots in {slots}')
-        spec = feature_spec(grid, out, test)
+        slots, examples = self._slot_list('replace_reference', slots, examples)
+        table = list(_feature_table((grid, out, test, POOL_NAMES if names is None else names), self.entries))
         landed = []
         for b, (s, ex) in enumerate(zip(slots, examples)):
-            new, fits = {}, 0 <= s < self.N
-            for name, (dtype, shape, crop, scale) in spec.items():
-                key = names.get(name, name)
-                e = self.entries[key]
-                want = PACKED_KIND.get(name, 'raw')
+            new = []
+            for name, key, _, kind, _, dtype, shape, crop, _ in table:
                 try:
                     a = np.ascontiguousarray(_decoded(ex[name], dtype, shape, crop))
                 except (ValueError, KeyError) as err:
                     raise ValueError(f'PoolLayout[{key!r}] scene {b}: {err}') from None
-                if e['kind'] != want or e['n'] != a.size or (want == 'raw' and e['dtype'] != dtype):
-                    raise ValueError(f"PoolLayout[{key!r}]: holds {e['kind']} scenes of {e['n']} elements, a replaced scene is {want} of {a.size}")
-                if want == 'bits':
-                    new[key] = (pack_bits(a),)
-                elif want == 'sparse':
-                    new[key] = pack_sparse(a)
-                    if fits and new[key][2].size > int(e['val_base'][s + 1] - e['val_base'][s]):
-                        fits = False
-                else:
-                    new[key] = (a.reshape(-1),)
-            landed.append(int(fits))
-            if not fits:
-                continue
-            for key, parts in new.items():
-                e = self.entries[key]
-                if e['kind'] == 'bits':
-                    e['words'][s] = parts[0]
-                elif e['kind'] == 'sparse':
-                    v0 = int(e['val_base'][s])
-                    e['mask'][s], e['offs'][s] = parts[0], parts[1]
-                    e['vals'][v0:v0 + parts[2].size] = parts[2]
-                else:
-                    e['data'][s] = parts[0]
+                new.append((key, (pack_bits(a),) if kind == 'bits' else pack_sparse(a) if kind == 'sparse' else (a.reshape(-1),)))
+            landed.append(self._write_slot(s, new))
         return landed
+
+    @staticmethod
+    def _slot_list(who, slots, examples):
+        slots, examples = [int(s) for s in slots], list(examples)
+        if len(slots) != len(examples):
+            raise ValueError(f'{who}: {len(slots)} slots for {len(examples)} scenes')
+        if len(set(slots)) != len(slots):
+            raise ValueError(f'{who}: duplicate slots in {slots}')
+        return slots, examples
+
+    def _write_slot(self, s, new):
+        """new: [(key, parts)] of one scene, parts as _packed_parts gives them.  -> 1 with every key of slot s replaced, or 0 with nothing
+        changed: a slot outside [0, N), or a sparse key with more value words than the slot holds."""
+        if not 0 <= s < self.N:
+            return 0
+        for key, parts in new:
+            e = self.entries[key]
+            if e['kind'] == 'sparse' and parts[2].size > int(e['val_base'][s + 1] - e['val_base'][s]):
+                return 0
+        for key, parts in new:
+            e = self.entries[key]
+            if e['kind'] == 'bits':
+                e['words'][s] = parts[0]
+            elif e['kind'] == 'sparse':
+                v0 = int(e['val_base'][s])
+                e['mask'][s], e['offs'][s] = parts[0], parts[1]
+                e['vals'][v0:v0 + parts[2].size] = parts[2]
+            else:
+                e['data'][s] = parts[0]
+        return 1
 
     def replace_packed_reference(self, slots, packed_examples, grid=512, out=256, test=False, names=None):
         """replace_reference for records that pack_example has already rewritten: the semantics of PoolWriter.put_packed and of a
@@ -1018,32 +1031,10 @@ class PoolLayout:
         writes, so replace_packed_reference(slots, [pack_example(e)]) leaves the layout byte-identical to replace_reference(slots, [e]).
         Every sparse stream is validated with check_sparse: a malformed record raises ValueError naming key and scene, before any slot
         changes.  -> [1 | 0] per scene."""
-        names = POOL_NAMES if names is None else names
-        slots = [int(s) for s in slots]
-        examples = list(packed_examples)
-        if len(slots) != len(examples):
-            raise ValueError(f'replace_packed_reference: {len(slots)} slots for {len(examples)} scenes')
-        if len(set(slots)) != len(slots):
-            raise ValueError(f'replace_packed_reference: duplicate slots in {slots}')
-        plan = []
-        for b, ex in enumerate(examples):
-            plan.append([(key, self.entries[key], parts) for key, parts in _packed_parts(ex, b, grid, out, test, names, self.entries)])
-        landed = []
-        for s, new in zip(slots, plan):
-            fits = 0 <= s < self.N and all(parts[2].size <= int(e['val_base'][s + 1] - e['val_base'][s]) for _, e, parts in new if e['kind'] == 'sparse')
-            landed.append(int(fits))
-            if not fits:
-                continue
-            for key, e, parts in new:
-                if e['kind'] == 'bits':
-                    e['words'][s] = parts[0]
-                elif e['kind'] == 'sparse':
-                    v0 = int(e['val_base'][s])
-                    e['mask'][s], e['offs'][s] = parts[0], parts[1]
-                    e['vals'][v0:v0 + parts[2].size] = parts[2]
-                else:
-                    e['data'][s] = parts[0]
-        return landed
+        slots, examples = self._slot_list('replace_packed_reference', slots, packed_examples)
+        table = list(_feature_table((grid, out, test, POOL_NAMES if names is None else names), self.entries))
+        plan = [_packed_parts(ex, b, table) for b, ex in enumerate(examples)]
+        return [self._write_slot(s, new) for s, new in zip(slots, plan)]
 
     def check_index(self, idx):
         """A host index list: ValueError unless every index is in [0, N).  -> int64 array."""
@@ -1138,30 +1129,35 @@ class ResidentPool:
     pool.window(B, source) is a ShuffleWindow: consumed slots refilled on a stream of its own while the step runs."""
 
     def __init__(self, layout, device='cuda', chunk_bytes=3 << 19):
-        dev = torch.device(device)
-        if dev.type != 'cuda':
-            raise RuntimeError('ResidentPool: CUDA (ROCm) device only: the HIP path has no CPU fallback')
+        dev = _hip_device('ResidentPool', device)
         if not layout.entries:
             raise ValueError('ResidentPool: an empty layout')
         self.layout, self.dev, self.N = layout, dev, layout.N
-        self.dev_arrays, self._staging = {}, []
-        copy = _copy_stream(dev)
-        self.up = torch.cuda.Event()
-        chunk = max(1, int(chunk_bytes))
-        with torch.cuda.stream(copy):
-            for key in layout.entries:
-                self.dev_arrays[key] = {}
-                for part, a in layout.arrays(key).items():
-                    nb = a.nbytes
-                    host = torch.empty((max(nb, 8),), dtype=torch.uint8).pin_memory()
-                    host.numpy()[:nb] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
-                    d = torch.empty((max(nb, 8),), dtype=torch.uint8, device=dev)          # never empty: a real pointer
-                    for i in range(0, nb, chunk):
-                        d[i:i + chunk].copy_(host[i:i + chunk], non_blocking=True)
-                    self._staging.append(host)
+        self.dev_arrays, self._staging = {key: {} for key in layout.entries}, []
+        self.up, self._ready = torch.cuda.Event(), False
+        if layout.device_only:                       # ResidentPool.empty: no host arrays, zero-filled here
+            for key, e in layout.entries.items():
+                for part, (shape, dt) in e['parts'].items():
+                    nb = int(np.prod(shape)) * np.dtype(dt).itemsize
+                    if part == 'val_base':
+                        d = (torch.arange(self.N + 1, dtype=torch.int64, device=dev) * e['capacity']).view(torch.uint8)
+                    else:
+                        d = torch.zeros((max(nb, 8),), dtype=torch.uint8, device=dev)          # never empty: a real pointer
                     self.dev_arrays[key][part] = d
-            self.up.record(copy)
-        self._ready = False
+            self.up.record(torch.cuda.current_stream(dev))
+        else:
+            copy = _copy_stream(dev)
+            with torch.cuda.stream(copy):
+                for key in layout.entries:
+                    for part, a in layout.arrays(key).items():
+                        nb = a.nbytes
+                        host = torch.empty((max(nb, 8),), dtype=torch.uint8).pin_memory()
+                        host.numpy()[:nb] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+                        d = torch.empty((max(nb, 8),), dtype=torch.uint8, device=dev)          # never empty: a real pointer
+                        _copy_chunked(d, host, nb, int(chunk_bytes))
+                        self._staging.append(host)
+                        self.dev_arrays[key][part] = d
+                self.up.record(copy)
 
     @classmethod
     def from_examples(cls, packed_examples, device='cuda', grid=512, out=256, test=False, names=None, chunk_bytes=3 << 19):
@@ -1171,29 +1167,12 @@ class ResidentPool:
     def empty(cls, N, device='cuda', grid=512, out=256, test=False, names=None, capacity=None):
         """ResidentPool(PoolLayout.empty(...)) without the host copy: the same arrays allocated on the device, zero-filled there (val_base
         computed there).  pool.layout then describes the keys (kind, n, shape, capacity) and holds no arrays."""
-        dev = torch.device(device)
-        if dev.type != 'cuda':
-            raise RuntimeError('ResidentPool: CUDA (ROCm) device only: the HIP path has no CPU fallback')
         lay = PoolLayout()
         lay.device_only, lay.N = True, int(N)
         lay.geometry = (grid, out, test, dict(POOL_NAMES if names is None else names))
-        self = cls.__new__(cls)
-        self.layout, self.dev, self.N = lay, dev, int(N)
-        self.dev_arrays, self._staging = {}, []
         for key, entry, parts in PoolLayout._empty_plan(N, grid, out, test, names, capacity):
             lay.entries[key] = dict(entry, parts=parts)
-            self.dev_arrays[key] = {}
-            for part, (shape, dt) in parts.items():
-                nb = int(np.prod(shape)) * np.dtype(dt).itemsize
-                if part == 'val_base':
-                    d = (torch.arange(int(N) + 1, dtype=torch.int64, device=dev) * entry['capacity']).view(torch.uint8)
-                else:
-                    d = torch.zeros((max(nb, 8),), dtype=torch.uint8, device=dev)          # never empty: a real pointer
-                self.dev_arrays[key][part] = d
-        self.up = torch.cuda.Event()
-        self.up.record(torch.cuda.current_stream(dev))
-        self._ready = False
-        return self
+        return cls(lay, device)
 
     def _n_vals(self, key):
         e = self.layout.entries[key]
@@ -1339,39 +1318,27 @@ class PoolWriter:
     ordered against that stream's gathers and is capturable in a graph (fill writer.raw[...] and writer.slots between replays): the counts
     of every sparse key, the admits, then the commit of every key.  It never waits for the device.  slots: a host list is range- and
     duplicate-checked (ValueError); a device int32 [B] tensor is trusted -- the kernels skip a slot outside the pool and report ok = 0;
-    duplicates in it are the caller's error.  The host arrays of pool.layout, where it has any, are not updated."""
+    duplicates in it are the caller's error.  The host arrays of pool.layout, where it has any, are not updated.
+    The writer is one upload handshake and the slots / ok tensors over a staging (_Stage): writer.unpacked for put / stage / commit (it owns
+    features, raw and offs_stage) and writer.packed for the *_packed twins."""
 
     def __init__(self, pool, B, chunk_bytes=3 << 19):
-        lay = pool.layout
-        if lay.geometry is None:
-            raise ValueError('PoolWriter: a pool laid out by PoolLayout.empty / from_examples (or ResidentPool.empty) only: the keys of a '
-                             'hand-built layout do not say which record feature they hold')
-        grid, out, test, names = lay.geometry
         self.pool, self.B, self.dev, self.chunk = pool, int(B), pool.dev, max(1, int(chunk_bytes))
         if self.B < 0:
             raise ValueError(f'PoolWriter: B {B}')
-        self.features = []                         # (record name, key, entry, nbytes, (T, H, W, C, y0, x0, Ho, Wo))
-        for name, (dtype, shape, crop, scale) in feature_spec(grid, out, test).items():
-            key = names.get(name, name)
-            e = lay.entries.get(key)
-            want = PACKED_KIND.get(name, 'raw')
-            n = int(np.prod(decoded_shape(shape, crop)))
-            if e is None or e['kind'] != want or e['n'] != n or (want == 'raw' and (e['dtype'] != dtype or crop is not None)):
-                raise ValueError(f"PoolWriter: pool key {key!r} is {None if e is None else (e['kind'], e['n'])}, raw records give {want} scenes of "
-                                 f'{n} elements: a pool of packed records (or ResidentPool.empty) only')
-            total = int(np.prod(shape))
-            geom = (1, 1, total, 1, 0, 0, 1, total) if crop is None else (shape[0], shape[1], shape[2], shape[3]) + tuple(crop)
-            self.features.append((name, key, e, total * ITEMSIZE[dtype], geom))
+        self.unpacked = _RawStage(pool, self.B, self.chunk)         # the staging of put / stage / commit
+        self.packed = None                                          # of put_packed / stage_packed / commit_packed: built on first use
+        self.features, self.raw, self.offs_stage = self.unpacked.features, self.unpacked.raw, self.unpacked.offs_stage
         rows = max(self.B, 1)                      # never empty: a real pointer, also with B = 0
-        self._host = {f[0]: torch.empty((rows, f[3]), dtype=torch.uint8).pin_memory() for f in self.features}
-        self.raw = {f[0]: torch.zeros((rows, f[3]), dtype=torch.uint8, device=self.dev)[:self.B] for f in self.features}
-        self.offs_stage = {key: torch.zeros((rows, -(-e['n'] // SPARSE_BLOCK) + 1), dtype=torch.int32, device=self.dev)
-                           for _, key, e, _, _ in self.features if e['kind'] == 'sparse'}
         self.ok = torch.zeros((rows,), dtype=torch.int32, device=self.dev)[:self.B]
         self.slots = torch.zeros((rows,), dtype=torch.int32, device=self.dev)[:self.B]
         self.copy = _copy_stream(self.dev)
-        self.up, self.done = torch.cuda.Event(), torch.cuda.Event()
-        self._pending = False                      # an upload from the pinned staging may still be running
+
+    def packed_stage(self):
+        """writer.packed, built on first use: its check(record, b) gives what stage_packed takes."""
+        if self.packed is None:
+            self.packed = _PackedStage(self.pool, self.B, self.chunk)
+        return self.packed
 
     def _set_slots(self, slots):
         if isinstance(slots, torch.Tensor) and slots.is_cuda:
@@ -1389,188 +1356,202 @@ class PoolWriter:
         if self.B:
             self.slots.copy_(torch.tensor(host, dtype=torch.int32))
 
-    def _check_records(self, examples):
+    # ---- the three steps, over either stage
+    def _checked(self, st, examples):
         examples = list(examples)
         if len(examples) != self.B:
             raise ValueError(f'PoolWriter: {len(examples)} records for a writer of {self.B} scenes')
-        for name, key, e, nbytes, _ in self.features:
-            for b, ex in enumerate(examples):
-                if name not in ex or len(ex[name]) != nbytes:
-                    raise ValueError(f"PoolWriter: feature {name} of scene {b}: {len(ex[name]) if name in ex else 'no'} bytes, expected {nbytes}")
-        return examples
+        return [st.check(ex, b) for b, ex in enumerate(examples)]
+
+    def _stage(self, st, parsed):
+        """The upload handshake: the pinned side of `st` is free once its previous upload has left it (a host wait on the copy alone); the
+        copy stream starts behind whatever read the device staging before (the previous commit, on the current stream); the current
+        stream waits for the copies (a device-side wait)."""
+        if len(parsed) != self.B:
+            raise ValueError(f'PoolWriter: {len(parsed)} records for a writer of {self.B} scenes')
+        if st.pending:
+            st.up.synchronize()
+        st.begin()
+        for b, p in enumerate(parsed):
+            st.fill(b, p)
+        main = torch.cuda.current_stream(self.dev)
+        st.done.record(main)
+        with torch.cuda.stream(self.copy):
+            self.copy.wait_event(st.done)
+            st.upload(self.B)
+            st.up.record(self.copy)
+        st.pending = True
+        main.wait_event(st.up)
+
+    def _commit(self, st, slots):
+        if slots is not None:
+            self._set_slots(slots)
+        self.pool._await_upload()
+        st.launch(_p(self.slots), self.B, _p(self.ok))
+        return self.ok
+
+    def _put(self, st, slots, examples):
+        parsed = self._checked(st, examples)
+        self._set_slots(slots)
+        self._stage(st, parsed)
+        return self._commit(st, None)
 
     def put(self, slots, examples):
         """examples: B parsed unpacked records ({feature: bytes}); scene b replaces pool slot slots[b].  -> writer.ok."""
-        examples = self._check_records(examples)
-        self._set_slots(slots)
-        self.stage(examples)
-        return self.commit()
+        return self._put(self.unpacked, slots, examples)
 
     def stage(self, examples):
         """The upload half of put(): the records' bytes into writer.raw through pinned memory on the copy stream; the current stream waits
         for them (a device-side wait), so a commit() issued next on it packs these records."""
-        examples = self._check_records(examples)
-        if self._pending:
-            self.up.synchronize()                  # the previous upload has left the pinned staging (a host wait on the copy alone)
-        for name, _, _, nbytes, _ in self.features:
-            h = self._host[name].numpy()
-            for b, ex in enumerate(examples):
-                h[b] = np.frombuffer(ex[name], np.uint8)
-        main = torch.cuda.current_stream(self.dev)
-        self.done.record(main)                     # whatever read writer.raw before (the previous commit) is in front of this
-        with torch.cuda.stream(self.copy):
-            self.copy.wait_event(self.done)
-            for name, _, _, nbytes, _ in self.features:
-                hs, ds = self._host[name].view(-1), self.raw[name].view(-1)
-                for i in range(0, ds.numel(), self.chunk):
-                    ds[i:i + self.chunk].copy_(hs[i:i + self.chunk], non_blocking=True)
-            self.up.record(self.copy)
-        self._pending = True
-        main.wait_event(self.up)
+        self._stage(self.unpacked, self._checked(self.unpacked, examples))
 
     def commit(self, slots=None):
         """Packs what writer.raw holds into the slots writer.slots names (slots: copied there first).  Launches only, on the current stream."""
-        if slots is not None:
-            self._set_slots(slots)
-        self.pool._await_upload()
-        B, N, st = self.B, self.pool.N, _st()
-        ok, sl, arrs = _p(self.ok), _p(self.slots), self.pool.dev_arrays
-        sparse = [f for f in self.features if f[2]['kind'] == 'sparse']
-        for name, key, e, _, geom in sparse:
-            call('stj_pack_sparse_count', _p(self.raw[name]), _p(self.offs_stage[key]), B, *geom, st)
-        for i, (name, key, e, _, geom) in enumerate(sparse):
-            call('stj_pool_admit', _p(self.offs_stage[key]), -(-e['n'] // SPARSE_BLOCK), _p(arrs[key]['val_base']), sl, N, ok, B, int(i == 0), st)
-        if not sparse:
-            call('stj_pool_admit', None, 0, None, sl, N, ok, B, 1, st)                      # the range check of the slots alone
-        for name, key, e, _, geom in self.features:
-            d = arrs[key]
-            if e['kind'] == 'bits':
-                call('stj_pack_bits', _p(self.raw[name]), ok, sl, N, _p(d['words']), B, *geom, st)
-            elif e['kind'] == 'sparse':
-                call('stj_pack_sparse_commit', _p(self.raw[name]), _p(self.offs_stage[key]), ok, sl, N, _p(d['mask']), _p(d['offs']),
-                     _p(d['val_base']), _p(d['vals']), self.pool._n_vals(key), B, *geom, st)
-            else:
-                call('stj_pool_put_raw', _p(self.raw[name]), ITEMSIZE[e['dtype']], ok, sl, N, _p(d['data']), B, e['n'], st)
-        return self.ok
+        return self._commit(self.unpacked, slots)
 
     # ---- records that pack_example has already rewritten: a scatter copy with no packing
-    def _packed_stage(self):
-        if getattr(self, 'packed', None) is None:
-            self.packed = _PackedStage(self.pool, self.B, self.chunk)
-            self._pup, self._pdone, self._ppending = torch.cuda.Event(), torch.cuda.Event(), False
-        return self.packed
-
     def put_packed(self, slots, packed_examples):
         """put() for B pack_example records: the packed planes go up as they are stored (a sparse plane: only its used words) and are
         copied into the slots -- stj_pool_admit_packed per sparse key, then stj_pool_put_raw for the fixed-length rows and stj_pool_put_vals
         for the value words.  PoolLayout.replace_packed_reference states the semantics.  Every stream is checked on the host first
         (check_sparse; ValueError naming key and scene, nothing launched).  -> writer.ok."""
-        examples = list(packed_examples)
-        if len(examples) != self.B:
-            raise ValueError(f'PoolWriter: {len(examples)} records for a writer of {self.B} scenes')
-        st = self._packed_stage()
-        parsed = [st.check(ex, b) for b, ex in enumerate(examples)]
-        self._set_slots(slots)
-        self.stage_packed(parsed)
-        return self.commit_packed()
+        return self._put(self.packed_stage(), slots, packed_examples)
 
     def stage_packed(self, parsed):
         """The upload half of put_packed(): parsed = [writer.packed.check(record, b)] into the device staging writer.packed.dev through
         pinned memory on the copy stream; the current stream waits for it."""
-        st = self._packed_stage()
-        if len(parsed) != self.B:
-            raise ValueError(f'PoolWriter: {len(parsed)} records for a writer of {self.B} scenes')
-        if self._ppending:
-            self._pup.synchronize()
-        st.begin()
-        for b, p in enumerate(parsed):
-            st.fill(b, p)
-        main = torch.cuda.current_stream(self.dev)
-        self._pdone.record(main)
-        with torch.cuda.stream(self.copy):
-            self.copy.wait_event(self._pdone)
-            st.upload(self.B)
-            self._pup.record(self.copy)
-        self._ppending = True
-        main.wait_event(self._pup)
+        self._stage(self.packed_stage(), parsed)
 
     def commit_packed(self, slots=None):
         """Copies what writer.packed.dev holds into the slots writer.slots names.  Launches only, on the current stream: capturable like
         commit() (stage_packed() between replays)."""
-        if slots is not None:
-            self._set_slots(slots)
-        self.pool._await_upload()
-        self._packed_stage().launch(_p(self.slots), self.B, _p(self.ok))
-        return self.ok
+        return self._commit(self.packed_stage(), slots)
 
 
-def _pieces(dst, src, count, chunk_bytes):
-    """dst[:count] <- src[:count] (flat tensors, host to device) in copies of at most chunk_bytes, on the current stream."""
-    step = max(1, chunk_bytes // src.element_size())
-    for i in range(0, count, step):
-        j = min(count, i + step)
-        dst[i:j].copy_(src[i:j], non_blocking=True)
+class _Stage:
+    """The staging of up to B records on their way into the slots of a pool, allocated once: what a PoolWriter holds per kind of record and
+    a ShuffleWindow twice.  _RawStage takes the reference's unpacked records, _PackedStage those pack_example has rewritten; both have
+    check(record, b)       one record validated on the host -> what fill() takes; ValueError naming the feature and scene b;
+    misfit(parsed)         None, or why no slot of the pool holds this record: a sparse key with more value words than a slot's capacity;
+    begin(), fill(b, parsed)     write the pinned side, scene by scene from 0;
+    upload(count)          the first `count` scenes to the device twins, in copies of at most chunk_bytes on the current stream;
+    launch(slots, count, ok)     slots, ok: device pointers (int32 [count]); the kernels, on the current stream: every admit runs before
+                           anything is written, so ok is final before the pool changes.
+    up / done / pending are the PoolWriter's handshake around upload(), one per stage."""
 
-
-class _PackedStage:
-    """The staging of up to B pack_example records on their way into the slots of a pool: per record feature pinned host arrays and
-    their device twins, allocated once, in the batch format of SparseHost and decode_batch_packed -- bits words [B][n / 32]; a sparse key's
-    mask [B][n / 32], scene-relative offs [B][nblk + 1], src_base int64 [B + 1] and vals, the scenes' value words back to back; the raw
-    rows [B][nbytes].  vals holds B x the slot capacity: a record that no slot can hold is never staged.
-    check(record, b) validates one record on the host, begin() / fill(b, parsed) write the pinned side, upload(count) copies the first
-    `count` scenes to the device on the current stream, launch(slots, count, ok) issues the admits and then the puts there."""
-
-    def __init__(self, pool, B, chunk_bytes=3 << 19):
+    def __init__(self, pool, B, chunk_bytes):
         lay = pool.layout
         if lay.geometry is None:
-            raise ValueError('packed staging: a pool laid out by PoolLayout.empty / from_examples (or ResidentPool.empty) only: the keys of a '
+            raise ValueError('PoolWriter: a pool laid out by PoolLayout.empty / from_examples (or ResidentPool.empty) only: the keys of a '
                              'hand-built layout do not say which record feature they hold')
         self.pool, self.B, self.dev, self.chunk = pool, int(B), pool.dev, max(1, int(chunk_bytes))
         self.geometry = lay.geometry
+        self.feats = list(_feature_table(lay.geometry, lay.entries))
+        self.capacity = {f.key: int(f.entry['capacity']) if lay.device_only else int(np.diff(f.entry['val_base']).min())
+                         for f in self.feats if f.kind == 'sparse'}
+        self.up, self.done, self.pending = torch.cuda.Event(), torch.cuda.Event(), False
+
+    def begin(self):
+        pass
+
+
+class _RawStage(_Stage):
+    """_Stage for parse_example records as the reference writes them: pinned rows and their device twins stage.raw[record name]
+    (uint8 [B, nbytes]), the offs_stage workspace of every sparse key; the kernels crop, bit-pack and stream-compact on the device."""
+
+    def __init__(self, pool, B, chunk_bytes=3 << 19):
+        super().__init__(pool, B, chunk_bytes)
+        self.features = []                         # (record name, key, entry, nbytes, (T, H, W, C, y0, x0, Ho, Wo))
+        for f in self.feats:
+            total = int(np.prod(f.shape))
+            geom = (1, 1, total, 1, 0, 0, 1, total) if f.crop is None else tuple(f.shape) + tuple(f.crop)
+            self.features.append((f.name, f.key, f.entry, total * ITEMSIZE[f.dtype], geom))
+        rows = max(self.B, 1)                      # never empty: a real pointer, also with B = 0
+        self.host = {f[0]: torch.empty((rows, f[3]), dtype=torch.uint8).pin_memory() for f in self.features}
+        self.raw = {f[0]: torch.zeros((rows, f[3]), dtype=torch.uint8, device=self.dev)[:self.B] for f in self.features}
+        self.offs_stage = {key: torch.zeros((rows, -(-e['n'] // SPARSE_BLOCK) + 1), dtype=torch.int32, device=self.dev)
+                           for _, key, e, _, _ in self.features if e['kind'] == 'sparse'}
+
+    def check(self, ex, b=0):
+        for name, _, _, nbytes, _ in self.features:
+            if name not in ex or len(ex[name]) != nbytes:
+                raise ValueError(f"feature {name} of scene {b}: {len(ex[name]) if name in ex else 'no'} bytes, expected {nbytes}")
+        return ex
+
+    def misfit(self, ex):
+        for f in self.feats:
+            if f.kind == 'sparse':
+                count = int(np.count_nonzero(_decoded(ex[f.name], f.dtype, f.shape, f.crop)))
+                if count > self.capacity[f.key]:
+                    return f'{f.key}: {count} value words, a slot holds {self.capacity[f.key]}'
+        return None
+
+    def fill(self, b, ex):
+        for name in self.host:
+            self.host[name].numpy()[b] = np.frombuffer(ex[name], np.uint8)
+
+    def upload(self, count):
+        for name, _, _, nbytes, _ in self.features:
+            _copy_chunked(self.raw[name].view(-1), self.host[name].view(-1), count * nbytes, self.chunk)
+
+    def launch(self, slots, count, ok):
+        """The counts of every sparse key, the admits, then the commit of every key."""
+        N, st, arrs = self.pool.N, _st(), self.pool.dev_arrays
+        sparse = [f for f in self.features if f[2]['kind'] == 'sparse']
+        for name, key, e, _, geom in sparse:
+            call('stj_pack_sparse_count', _p(self.raw[name]), _p(self.offs_stage[key]), count, *geom, st)
+        for i, (name, key, e, _, geom) in enumerate(sparse):
+            call('stj_pool_admit', _p(self.offs_stage[key]), -(-e['n'] // SPARSE_BLOCK), _p(arrs[key]['val_base']), slots, N, ok, count, int(i == 0), st)
+        if not sparse:
+            call('stj_pool_admit', None, 0, None, slots, N, ok, count, 1, st)                # the range check of the slots alone
+        for name, key, e, _, geom in self.features:
+            d = arrs[key]
+            if e['kind'] == 'bits':
+                call('stj_pack_bits', _p(self.raw[name]), ok, slots, N, _p(d['words']), count, *geom, st)
+            elif e['kind'] == 'sparse':
+                call('stj_pack_sparse_commit', _p(self.raw[name]), _p(self.offs_stage[key]), ok, slots, N, _p(d['mask']), _p(d['offs']),
+                     _p(d['val_base']), _p(d['vals']), self.pool._n_vals(key), count, *geom, st)
+            else:
+                call('stj_pool_put_raw', _p(self.raw[name]), ITEMSIZE[e['dtype']], ok, slots, N, _p(d['data']), count, e['n'], st)
+
+
+class _PackedStage(_Stage):
+    """_Stage for pack_example records: per record feature pinned host arrays and their device twins in the batch format of SparseHost
+    and decode_batch_packed -- bits words [B][n / 32]; a sparse key's mask [B][n / 32], scene-relative offs [B][nblk + 1], src_base int64
+    [B + 1] and vals, the scenes' value words back to back; the raw rows [B][nbytes].  vals holds B x the slot capacity: a record that no
+    slot can hold is never staged.  launch() is a scatter copy with no packing: the admits, then the puts."""
+
+    def __init__(self, pool, B, chunk_bytes=3 << 19):
+        super().__init__(pool, B, chunk_bytes)
         rows = max(self.B, 1)
-        self.feats, self.capacity, self.host, self.dev_bufs = [], {}, {}, {}
-        grid, out, test, names = lay.geometry
-        for name, (dtype, shape, crop, scale) in feature_spec(grid, out, test).items():
-            key = names.get(name, name)
-            e = lay.entries.get(key)
-            kind = PACKED_KIND.get(name, 'raw')
-            n = int(np.prod(decoded_shape(shape, crop)))
-            if e is None or e['kind'] != kind or e['n'] != n or (kind == 'raw' and (e['dtype'] != dtype or crop is not None)):
-                raise ValueError(f"packed staging: pool key {key!r} is {None if e is None else (e['kind'], e['n'])}, packed records give {kind} "
-                                 f'scenes of {n} elements')
-            self.feats.append((name, key, e, kind, n))
+        self.host, self.dev_bufs = {}, {}
+        for name, key, e, kind, n, dtype, *_ in self.feats:
             if kind == 'bits':
                 sizes = {'bits': (rows * (n // 32), torch.int32)}
             elif kind == 'sparse':
-                cap = int(e['capacity']) if lay.device_only else int(np.diff(e['val_base']).min())
-                self.capacity[key] = cap
                 sizes = {'mask': (rows * (n // 32), torch.int32), 'offs': (rows * (-(-n // SPARSE_BLOCK) + 1), torch.int32),
-                         'base': (rows + 1, torch.int64), 'vals': (max(rows * cap, 1), torch.int32)}
+                         'base': (rows + 1, torch.int64), 'vals': (max(rows * self.capacity[key], 1), torch.int32)}
             else:
                 sizes = {'raw': (rows * n * ITEMSIZE[dtype], torch.uint8)}
             for part, (count, dt) in sizes.items():
                 self.host[name, part] = torch.zeros((max(count, 1),), dtype=dt).pin_memory()
                 self.dev_bufs[name, part] = torch.zeros((max(count, 1),), dtype=dt, device=self.dev)
-        self.dev = pool.dev
         self._base = {}
 
     def check(self, ex, b=0):
-        """One pack_example record -> its arrays as fill() takes them; ValueError naming key and scene for a malformed one."""
-        grid, out, test, names = self.geometry
-        return _packed_parts(ex, b, grid, out, test, names, self.pool.layout.entries)
+        return _packed_parts(ex, b, self.feats)
 
     def misfit(self, parsed):
-        """None, or why no slot of the pool holds this record: a sparse key with more value words than a slot's capacity."""
-        for (name, key, e, kind, n), (_, parts) in zip(self.feats, parsed):
+        for (name, key, e, kind, *_), (_, parts) in zip(self.feats, parsed):
             if kind == 'sparse' and parts[2].size > self.capacity[key]:
                 return f'{key}: {parts[2].size} value words, a slot holds {self.capacity[key]}'
         return None
 
     def begin(self):
-        self._base = {name: [0] for name, _, _, kind, _ in self.feats if kind == 'sparse'}
+        self._base = {f.name: [0] for f in self.feats if f.kind == 'sparse'}
 
     def fill(self, b, parsed):
-        for (name, key, e, kind, n), (_, parts) in zip(self.feats, parsed):
+        for (name, key, e, kind, n, *_), (_, parts) in zip(self.feats, parsed):
             if kind == 'bits':
                 _put(self.host[name, 'bits'], b * (n // 32), parts[0])
             elif kind == 'sparse':
@@ -1588,37 +1569,19 @@ class _PackedStage:
                 self.host[name, 'raw'].numpy()[b * raw.size:(b + 1) * raw.size] = raw
 
     def upload(self, count):
-        for name, key, e, kind, n in self.feats:
-            for part in {'bits': ('bits',), 'sparse': ('mask', 'offs', 'base', 'vals'), 'raw': ('raw',)}[kind]:
-                h = self.host[name, part]
-                if part == 'base':
-                    k = count + 1
-                elif part == 'vals':
-                    k = self._base[name][count]
-                else:
-                    k = (h.numel() // max(self.B, 1)) * count
-                _pieces(self.dev_bufs[name, part], h, k, self.chunk)
-
-    def upload_bytes(self, count):
-        """Bytes upload(count) moves, as the pinned side stands."""
-        total = 0
-        for name, key, e, kind, n in self.feats:
-            for part in {'bits': ('bits',), 'sparse': ('mask', 'offs', 'base', 'vals'), 'raw': ('raw',)}[kind]:
-                h = self.host[name, part]
-                k = count + 1 if part == 'base' else self._base[name][count] if part == 'vals' else (h.numel() // max(self.B, 1)) * count
-                total += k * h.element_size()
-        return total
+        for (name, part), h in self.host.items():
+            k = count + 1 if part == 'base' else self._base[name][count] if part == 'vals' else (h.numel() // max(self.B, 1)) * count
+            _copy_chunked(self.dev_bufs[name, part], h, k, self.chunk)
 
     def launch(self, slots, count, ok):
-        """slots, ok: device pointers (int32 [count]).  Every admit runs before any put, so ok is final before the pool is written."""
         N, st, arrs, d = self.pool.N, _st(), self.pool.dev_arrays, self.dev_bufs
-        sparse = [f for f in self.feats if f[3] == 'sparse']
-        for i, (name, key, e, _, n) in enumerate(sparse):
+        sparse = [f for f in self.feats if f.kind == 'sparse']
+        for i, (name, key, e, _, n, *_) in enumerate(sparse):
             call('stj_pool_admit_packed', _p(d[name, 'offs']), -(-n // SPARSE_BLOCK), n, _p(d[name, 'base']), _p(arrs[key]['val_base']), slots, N, ok,
                  count, int(i == 0), st)
         if not sparse:
             call('stj_pool_admit', None, 0, None, slots, N, ok, count, 1, st)
-        for name, key, e, kind, n in self.feats:
+        for name, key, e, kind, n, *_ in self.feats:
             a = arrs[key]
             if kind == 'bits':
                 call('stj_pool_put_raw', _p(d[name, 'bits']), 4, ok, slots, N, _p(a['words']), count, n // 32, st)
@@ -1693,17 +1656,9 @@ class ShuffleWindow:
         self.tail = self.head = self.n_live = 0
         self.consumed = self.stalls = self.steps = 0
         self.skipped = []
-        if self.packed:
-            self._sets = [_PackedStage(pool, B, chunk_bytes) for _ in range(2)]
-            self._ok = [torch.zeros((B,), dtype=torch.int32, device=self.dev) for _ in self._sets]
-            self._free = [None for _ in self._sets]           # the event behind the last upload from a set's pinned side
-            self._checker = self._sets[0]
-        else:
-            self._sets = [PoolWriter(pool, B, chunk_bytes) for _ in range(2)]
-            self._raw_feats = [(name, key, e, nbytes) for name, key, e, nbytes, _ in self._sets[0].features]
-            lay = pool.layout
-            self._capacity = {key: int(e['capacity']) if lay.device_only else int(np.diff(e['val_base']).min())
-                              for _, key, e, _ in self._raw_feats if e['kind'] == 'sparse'}
+        self._sets = [(_PackedStage if self.packed else _RawStage)(pool, B, chunk_bytes) for _ in range(2)]       # two staging sets
+        self._ok = [torch.zeros((B,), dtype=torch.int32, device=self.dev) for _ in self._sets]
+        self._free = [None for _ in self._sets]               # the event behind the last upload from a set's pinned side
         self._q, self._pending, self._open = queue.Queue(), collections.deque(), None
         self._ordinal, self._dry, self._stop, self._err, self._done = 0, False, False, None, False
         self._thread = threading.Thread(target=self._run, daemon=True)
@@ -1765,23 +1720,11 @@ class ShuffleWindow:
 
     # ---- the worker
     def _validate(self, ex):
-        if self.packed:
-            parsed = self._checker.check(ex, 0)
-            why = self._checker.misfit(parsed)
-            if why is not None:
-                raise ValueError(why)
-            return parsed
-        grid, out, test, _ = self.pool.layout.geometry
-        spec = feature_spec(grid, out, test)
-        for name, key, e, nbytes in self._raw_feats:
-            if name not in ex or len(ex[name]) != nbytes:
-                raise ValueError(f"feature {name}: {len(ex[name]) if name in ex else 'no'} bytes, expected {nbytes}")
-            if e['kind'] == 'sparse':
-                dtype, shape, crop, _ = spec[name]
-                count = int(np.count_nonzero(_decoded(ex[name], dtype, shape, crop)))
-                if count > self._capacity[key]:
-                    raise ValueError(f'{key}: {count} value words, a slot holds {self._capacity[key]}')
-        return ex
+        parsed = self._sets[0].check(ex, 0)
+        why = self._sets[0].misfit(parsed)
+        if why is not None:
+            raise ValueError(why)
+        return parsed
 
     def _pull(self):
         """The next B records of the source that can land (fewer at its end); the others go to window.skipped."""
@@ -1801,7 +1744,7 @@ class ShuffleWindow:
 
     def _prepare(self, k):
         recs = self._pull()
-        if self.packed and recs:
+        if recs:
             if self._free[k] is not None:
                 self._free[k].synchronize()                   # the set's previous upload has left its pinned side
             st = self._sets[k]
@@ -1811,30 +1754,19 @@ class ShuffleWindow:
         return recs
 
     def _commit(self, g, k, recs):
-        r, B = len(recs), self.B
+        r = len(recs)
         g.count = r
         if not r:
             return
         with torch.cuda.stream(self.refill):
             slots = self.perm[g.pos:g.pos + r]
-            if self.packed:
-                st, ok = self._sets[k], self._ok[k]
-                st.upload(r)
-                self._free[k] = torch.cuda.Event()
-                self._free[k].record(self.refill)
-                if g.after is not None:
-                    self.refill.wait_event(g.after)           # the gathers that read these slots are done
-                st.launch(_p(slots), r, _p(ok))
-            else:
-                w = self._sets[k]
-                ok = w.ok
-                w.stage(recs + [recs[-1]] * (B - r))
-                if g.after is not None:
-                    self.refill.wait_event(g.after)
-                w.slots[:r].copy_(slots, non_blocking=True)
-                if r < B:
-                    w.slots[r:].fill_(-1)                     # rows behind the source's end: skipped by every kernel
-                w.commit()
+            st, ok = self._sets[k], self._ok[k]
+            st.upload(r)
+            self._free[k] = torch.cuda.Event()
+            self._free[k].record(self.refill)
+            if g.after is not None:
+                self.refill.wait_event(g.after)               # the gathers that read these slots are done
+            st.launch(_p(slots), r, _p(ok))
             self.bad.add_(r - ok[:r].sum(dtype=torch.int32))
             g.done = torch.cuda.Event()
             g.done.record(self.refill)

@@ -118,3 +118,34 @@ def test_sampler_on_the_cpu_device():
     assert torch.cat(D.PoolSampler(N, B, 'cpu', shuffle=False).epoch()).tolist() == list(range(9))
     with pytest.raises(ValueError):
         D.PoolSampler(2, 3, 'cpu')
+
+
+@pytest.mark.parametrize('test', [False, True])
+def test_feature_table_is_the_layouts_keys_and_refuses_another_layout(test):
+    """The one walk from record features to pool keys: over PoolLayout.empty it yields exactly the layout's keys with their kind and n, and
+    a key of another kind, size or dtype raises ValueError naming the key."""
+    lay = D.PoolLayout.empty(1, 64, 32, test)
+    spec = D.feature_spec(64, 32, test)
+    rows = list(D._feature_table(lay.geometry, lay.entries))
+    assert [f.name for f in rows] == list(spec) and [f.key for f in rows] == list(lay.entries)
+    for f in rows:
+        e = lay.entries[f.key]
+        assert f.entry is e and (f.kind, f.n) == (e['kind'], e['n']) and f.key == D.POOL_NAMES[f.name], f.name
+        assert (f.dtype, f.shape, f.crop, f.scale) == spec[f.name] and f.n == int(np.prod(D.decoded_shape(f.shape, f.crop))), f.name
+        assert f.kind == D.PACKED_KIND.get(f.name, 'raw') and (f.kind != 'raw' or e['dtype'] == f.dtype), f.name
+    free = list(D._feature_table(lay.geometry))                                        # without entries: the same rows, nothing checked
+    assert [(f.name, f.key, f.kind, f.n) for f in free] == [(f.name, f.key, f.kind, f.n) for f in rows] and all(f.entry is None for f in free)
+    n = lay.entries['flow']['n']
+    zero = np.zeros(n, np.float32)
+    others = {'bits': D.PoolLayout().add_bits('flow', [D.pack_bits(zero)]),
+              'another n': D.PoolLayout().add_sparse('flow', [D.pack_sparse(zero[:n // 2])], n // 2),
+              'raw float64': D.PoolLayout().add_raw('flow', [zero.astype(np.float64)], 'float64'),
+              'missing': D.PoolLayout()}
+    for what, other in others.items():
+        entries = {k: e for k, e in lay.entries.items() if k != 'flow'}
+        entries.update(other.entries)
+        with pytest.raises(ValueError, match="'flow'"):
+            list(D._feature_table(lay.geometry, entries))
+    wrong = dict(lay.entries, map_img=D.PoolLayout().add_raw('map_img', [np.zeros(lay.entries['map_img']['n'], np.uint8)], 'bool').entries['map_img'])
+    with pytest.raises(ValueError, match="'map_img'"):                                  # a raw key of the right size and another dtype
+        list(D._feature_table(lay.geometry, wrong))

@@ -148,7 +148,7 @@ def test_commit_packed_captures_and_replays(lib_built):
     pool = D.ResidentPool.empty(4, 'cuda', G, O)
     pool.wait()
     w = pool.writer(2)
-    check = lambda exs: [w._packed_stage().check(ex, b) for b, ex in enumerate(exs)]
+    check = lambda exs: [w.packed_stage().check(ex, b) for b, ex in enumerate(exs)]
     w.stage_packed(check(packed[:2]))
     w.slots.copy_(dev_i32([0, 1]))
     side = torch.cuda.Stream()

@@ -332,10 +332,7 @@ if a.replace_put:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with torch.cuda.stream(w.copy):                                  # the H2D copies of stage() again, without its host-side fill
             e0.record(w.copy)
-            for name in w.raw:
-                hs, ds = w._host[name].view(-1), w.raw[name].view(-1)
-                for i in range(0, ds.numel(), w.chunk):
-                    ds[i:i + w.chunk].copy_(hs[i:i + w.chunk], non_blocking=True)
+            w.unpacked.upload(B)
             e1.record(w.copy)
         torch.cuda.synchronize()
         t_h2d.append(e0.elapsed_time(e1) * 1e-3)
