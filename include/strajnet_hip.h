@@ -464,6 +464,16 @@ int stj_compress_sizes(int B, int Tn, int H, int W, long long* work_bytes, long 
 int stj_compress_waypoints(const uint8_t* Q, void* work, uint8_t* out, uint32_t* offsets, int B, int Tn, int H, int W, hipStream_t stream);
 int stj_compress_waypoints_level(const uint8_t* Q, void* work, uint8_t* out, uint32_t* offsets, int B, int Tn, int H, int W, int level,
                                  hipStream_t stream);
+/* The same streams inside their protobuf framing (strajnet_amd/csrc/frame.h; frame_reference in strajnet_amd/submission.py): per scene and
+ * waypoint `tag_wp varint(Lk)`, then per field `tag varint(l) <stream>` -- a scene's block is the wire form of its repeated Waypoint
+ * field as it stands.  tags: the four tag bytes, tag_wp | tag_obs << 8 | tag_occ << 16 | tag_flow << 24.  table uint32
+ * [6*B*Tn + B + 1]: stream starts [3*B*Tn] (of the zlib bytes, behind their header), stream lengths [3*B*Tn], scene starts [B + 1]
+ * (the last: the total).  stj_compress_framed_sizes: scratch bytes (= stj_compress_sizes'), the capacity of `out` (stj_compress_sizes'
+ * + 6 per stream and 6 per waypoint) and the table's words.  Level, shape limits and codes of stj_compress_waypoints_level; the same
+ * encode and pack launches with another offsets kernel between them: three launches, no host synchronisation, no allocation. */
+int stj_compress_framed_sizes(int B, int Tn, int H, int W, long long* work_bytes, long long* out_capacity, long long* table_words);
+int stj_compress_waypoints_framed(const uint8_t* Q, void* work, uint8_t* out, uint32_t* table, int B, int Tn, int H, int W, int level,
+                                  uint32_t tags, hipStream_t stream);
 int stj_outconv_bwd(const void* X, const float* W, const float* dY, void* dX, float* dW, float* db, int F, int Hh, int Ww,
                     int C, int Tn, long long y_bstride, long long y_tstride, long long y_pstride, int elu_in, void* ws,
                     long long ws_bytes, int dtype, hipStream_t stream);

@@ -13,5 +13,6 @@ from .metrics import compute_occupancy_flow_metrics, apply_sigmoid_to_occupancy_
 from .evaluate import Mean, OGMFlowMetrics, SceneScores, print_metrics, eval_step     # noqa: F401
 from .submission import (QuantizedWaypoints, ResultDrain, quantize_waypoints, quantize_reference,     # noqa: F401
                          compress_batch, compression_pool, CompressedWaypoints, compress_waypoints, compress_reference,
-                         DEFLATE_SEGMENT)
+                         DEFLATE_SEGMENT, FramedWaypoints, SubmissionWriter, SUBMISSION_SCHEMA, frame_reference,
+                         submission_reference, parse_submission)
 from .data import (ResidentPool, ResidentFeed, PoolLayout, PoolWriter, PoolSampler, ShuffleWindow, WindowFeed)     # noqa: F401

@@ -14,7 +14,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'strajnet_hip.h')
 LIB_PATH = os.environ.get('STJ_LIB_PATH') or os.path.join(_HERE, 'libstrajnet_hip.so')     # override: A/B runs of two builds
 
 vp, ci, cl, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
-_SCALARS = {'int': ci, 'long long': cl, 'float': cf, 'hipStream_t': vp}
+_SCALARS = {'int': ci, 'long long': cl, 'float': cf, 'uint32_t': ctypes.c_uint32, 'hipStream_t': vp}
 
 
 class StjError(RuntimeError):

@@ -9,6 +9,8 @@
 //                           fixed and dynamic-Huffman forms (the code is built per segment; the per-symbol rules: deflate_dyn.h)
 //   deflate_offsets_kernel  one workgroup: per plane the scan of its segments' byte counts and its Adler-32, the scan of the planes'
 //                           totals -> `offsets`, and every stream's header and trailer
+//   deflate_offsets_framed_kernel  the same for stj_compress_waypoints_framed: + room for, and the bytes of, the protobuf header in front
+//                           of every stream and waypoint (frame.h), stream starts, lengths and scene starts -> the framed table
 //   deflate_pack_kernel     one workgroup per (plane, segment): the slot's bytes to their place in the packed buffer
 //
 // Workspace: [ segment table, 4 uint32 per segment: bytes, byte sum, weighted byte sum, offset in its stream | slots of DF_SLOT bytes ];
@@ -17,6 +19,7 @@
 #include "common.h"
 #include "deflate.h"
 #include "deflate_dyn.h"
+#include "frame.h"
 
 static_assert(DF_SEG >= 4096 && DF_SEG <= 16384 && (DF_SEG & (DF_SEG - 1)) == 0, "DF_SEG: a power of two, 64 KB of static LDS at most");
 constexpr int DF_NW = DF_NT / 64;          // waves per workgroup
@@ -445,33 +448,37 @@ __global__ __launch_bounds__(DF_NT) void deflate_encode_dyn_kernel(const uint8_t
   }
 }
 
+// Stream p of the batch: the scan of its segments' byte counts (each segment's offset in the stream into its table entry, behind the two
+// header bytes) and its Adler-32 from the segments' partial sums.  Returns the stream's length, header and trailer included.
+__device__ __forceinline__ uint32_t df_stream_scan(uint32_t* __restrict__ table, int p, int HW, int nso, int nsf, uint32_t* adler) {
+  const int sps = 16 * nso + 8 * nsf;
+  const int b = p / 24, k = (p % 24) / 3, f = p % 3;
+  const int ns = f < 2 ? nso : nsf, n = f < 2 ? HW : 2 * HW;
+  uint32_t* t = table + 4 * ((long long)b * sps + (f < 2 ? (f * 8 + k) * nso : 16 * nso + k * nsf));
+  uint32_t A = 1, Bs = 0, acc = 2;
+  for (int s = 0; s < ns; ++s) {
+    const uint32_t L = (uint32_t)min(DF_SEG, n - s * DF_SEG);
+    t[4 * s + 3] = acc;
+    acc += t[4 * s];
+    Bs = (Bs + L * A + t[4 * s + 2]) % DF_ADLER;          // L * A < 2^14 * 2^16
+    A = (A + t[4 * s + 1]) % DF_ADLER;
+  }
+  *adler = Bs << 16 | A;
+  return acc + 4;
+}
+
 // One workgroup of 1024: thread <-> stream, in chunks of 1024 streams with a running carry.
 __global__ __launch_bounds__(1024) void deflate_offsets_kernel(uint32_t* __restrict__ table, uint8_t* __restrict__ out, uint32_t* __restrict__ offsets,
                                                                int P, int HW, int nso, int nsf) {
   __shared__ uint32_t ws[16];
   __shared__ uint32_t carry;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int sps = 16 * nso + 8 * nsf;
   if (tid == 0) carry = 0;
   __syncthreads();
   for (int p0 = 0; p0 < P; p0 += 1024) {
     const int p = p0 + tid;
     uint32_t total = 0, adler = 1;
-    if (p < P) {
-      const int b = p / 24, k = (p % 24) / 3, f = p % 3;
-      const int ns = f < 2 ? nso : nsf, n = f < 2 ? HW : 2 * HW;
-      uint32_t* t = table + 4 * ((long long)b * sps + (f < 2 ? (f * 8 + k) * nso : 16 * nso + k * nsf));
-      uint32_t A = 1, Bs = 0, acc = 2;
-      for (int s = 0; s < ns; ++s) {
-        const uint32_t L = (uint32_t)min(DF_SEG, n - s * DF_SEG);
-        t[4 * s + 3] = acc;
-        acc += t[4 * s];
-        Bs = (Bs + L * A + t[4 * s + 2]) % DF_ADLER;          // L * A < 2^14 * 2^16
-        A = (A + t[4 * s + 1]) % DF_ADLER;
-      }
-      total = acc + 4;
-      adler = Bs << 16 | A;
-    }
+    if (p < P) total = df_stream_scan(table, p, HW, nso, nsf, &adler);
     uint32_t inc = total;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -493,6 +500,92 @@ __global__ __launch_bounds__(1024) void deflate_offsets_kernel(uint32_t* __restr
     __syncthreads();
   }
   if (tid == 0) offsets[P] = carry;
+}
+
+// deflate_offsets_kernel for the framed layout (frame.h): besides each stream's scan, header and trailer, the protobuf header in front of
+// every stream and every waypoint.  One workgroup of 1024, thread <-> stream in chunks of DFF_CHUNK = 1008 = 42 scenes, so that a
+// waypoint's three streams and a scene's 24 always lie in one chunk (1024 is a multiple of neither); a waypoint's body length is read
+// from its three threads' field lengths in LDS, and ONE scan then runs over the extents (the stream's field, + the waypoint's header on
+// its first stream).  ftable: [ stream starts P | stream lengths P | scene starts P / 24 + 1 ]; the starts are what deflate_pack_kernel
+// takes for `offsets`.
+// A thread's header bytes, at most 2 * FRM_MAX_HEADER + 2, gathered in registers and written with two stores that may overlap: a store
+// instruction per byte, each to 64 different cache lines per wave, put the chain outside its gate.  Byte addresses, so the
+// stores are unaligned ones.
+struct DffBytes {
+  uint64_t lo = 0, hi = 0;
+  uint32_t n = 0;
+  __device__ __forceinline__ void put(uint8_t b) {
+    if (n < 8) lo |= (uint64_t)b << (8 * n); else hi |= (uint64_t)b << (8 * (n - 8));
+    ++n;
+  }
+  __device__ __forceinline__ void put_varint(uint32_t v) {
+    for (; v >= 0x80u; v >>= 7) put((uint8_t)(v | 0x80u));
+    put((uint8_t)v);
+  }
+  __device__ __forceinline__ void store(uint8_t* q) const {             // 4 <= n <= 16
+    if (n >= 8) {
+      const uint32_t sh = 8 * (n - 8);
+      const uint64_t tail = sh == 0 ? lo : sh == 64 ? hi : lo >> sh | hi << (64 - sh);
+      __builtin_memcpy(q, &lo, 8);
+      __builtin_memcpy(q + n - 8, &tail, 8);
+    } else {
+      const uint32_t head = (uint32_t)lo, tail = (uint32_t)(lo >> (8 * (n - 4)));
+      __builtin_memcpy(q, &head, 4);
+      __builtin_memcpy(q + n - 4, &tail, 4);
+    }
+  }
+};
+constexpr int DFF_CHUNK = 1008;
+static_assert(DFF_CHUNK % 24 == 0 && DFF_CHUNK <= 1024, "whole scenes per chunk");
+__global__ __launch_bounds__(1024) void deflate_offsets_framed_kernel(uint32_t* __restrict__ table, uint8_t* __restrict__ out, uint32_t* __restrict__ ftable,
+                                                                      int P, int HW, int nso, int nsf, uint32_t tags) {
+  __shared__ uint32_t ws[16];
+  __shared__ uint32_t fl[1024];
+  __shared__ uint32_t carry;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int f = tid % 3;                                   // (= p % 3: a chunk starts with a scene)
+  if (tid == 0) carry = 0;
+  for (int p0 = 0; p0 < P; p0 += DFF_CHUNK) {
+    const int p = p0 + tid;
+    const bool live = tid < DFF_CHUNK && p < P;
+    uint32_t total = 0, adler = 1, field = 0;
+    if (live) { total = df_stream_scan(table, p, HW, nso, nsf, &adler); field = frm_field_len(total); }
+    fl[tid] = field;
+    __syncthreads();
+    uint32_t body = 0, ext = field;
+    if (live && f == 0) { body = field + fl[tid + 1] + fl[tid + 2]; ext += 1u + pb_varint_len(body); }      // tid + 2 <= 1007
+    uint32_t inc = ext;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t y = __shfl_up(inc, o);
+      if (lane >= o) inc += y;
+    }
+    if (lane == 63) ws[wv] = inc;
+    __syncthreads();
+    uint32_t off = carry + inc - ext;
+    for (int k = 0; k < wv; ++k) off += ws[k];
+    if (live) {
+      DffBytes h;
+      if (f == 0) {
+        if (tid % 24 == 0) ftable[2 * P + p / 24] = off;
+        h.put(frm_tag(tags, 0));
+        h.put_varint(body);
+      }
+      h.put(frm_tag(tags, 1 + f));
+      h.put_varint(total);
+      const uint32_t start = off + h.n;
+      ftable[p] = start;
+      ftable[P + p] = total;
+      h.put(0x78); h.put(0x01);
+      h.store(out + off);
+      const uint32_t be = __builtin_bswap32(adler);
+      __builtin_memcpy(out + start + total - 4, &be, 4);
+    }
+    __syncthreads();
+    if (tid == 1023) carry = off + ext;                    // (ext = 0 here: the chunk's end)
+  }
+  __syncthreads();
+  if (tid == 0) ftable[2 * P + P / 24] = carry;
 }
 
 // The slot's bytes to out + offsets[stream] + (offset in the stream): whole aligned 16-byte vectors of the destination are composed from
@@ -529,7 +622,7 @@ __global__ __launch_bounds__(256) void deflate_pack_kernel(const uint8_t* __rest
   }
 }
 
-static int df_shape(const char* who, int B, int Tn, int Hh, int Ww, long long* nseg, long long* cap, int* nso, int* nsf) {
+static int df_shape(const char* who, int B, int Tn, int Hh, int Ww, bool framed, long long* nseg, long long* cap, int* nso, int* nsf) {
   if (B <= 0 || Hh <= 0 || Ww <= 0) { stj_set_error("%s: empty problem", who); return STJ_EINVAL; }
   const long long HW = (long long)Hh * Ww;
   if (Tn != 8 || HW % 256 || HW > (1 << 28)) {
@@ -540,6 +633,7 @@ static int df_shape(const char* who, int B, int Tn, int Hh, int Ww, long long* n
   *nsf = (int)((2 * HW + DF_SEG - 1) / DF_SEG);
   *nseg = (long long)B * (16 * *nso + 8 * *nsf);
   *cap = (long long)B * (32 * HW + 5ll * (16 * *nso + 8 * *nsf) + 6 * 24);            // n + 5 ceil(n / DF_SEG) + 6 per stream
+  if (framed) *cap += (long long)B * FRM_MAX_HEADER * (24 + 8);                          // + a header per stream and per waypoint (frame.h)
   if (*nseg > 0x7fffffffLL || *cap > 0xffffffffLL) {
     stj_set_error("%s: batch too large for 32-bit stream offsets (B %d, H %d, W %d)", who, B, Hh, Ww);
     return STJ_EUNSUPPORTED;
@@ -550,18 +644,19 @@ static inline long long df_table_bytes(long long nseg) { return (nseg * 16 + 255
 
 extern "C" int stj_compress_sizes(int B, int Tn, int H, int W, long long* work_bytes, long long* out_capacity) {
   long long nseg, cap; int nso, nsf;
-  const int rc = df_shape("stj_compress_sizes", B, Tn, H, W, &nseg, &cap, &nso, &nsf);
+  const int rc = df_shape("stj_compress_sizes", B, Tn, H, W, false, &nseg, &cap, &nso, &nsf);
   if (rc != STJ_OK) return rc;
   *work_bytes = df_table_bytes(nseg) + nseg * DF_SLOT;
   *out_capacity = (cap + 15) / 16 * 16;
   return STJ_OK;
 }
 
+// `framed`: `offsets` is the framed table (stream starts first: what the pack kernel reads), `tags` the four tag bytes.
 static int df_launch(const char* who, const uint8_t* Q, void* work, uint8_t* out, uint32_t* offsets, int B, int Tn, int H, int W, int level,
-                     hipStream_t stream) {
+                     bool framed, uint32_t tags, hipStream_t stream) {
   if (level != 1 && level != 2) { stj_set_error("%s: level 1 (fixed Huffman code) or 2 (dynamic per segment), got %d", who, level); return STJ_EINVAL; }
   long long nseg, cap; int nso, nsf;
-  const int rc = df_shape(who, B, Tn, H, W, &nseg, &cap, &nso, &nsf);
+  const int rc = df_shape(who, B, Tn, H, W, framed, &nseg, &cap, &nso, &nsf);
   if (rc != STJ_OK) return rc;
   if (((uintptr_t)Q | (uintptr_t)work | (uintptr_t)out | (uintptr_t)offsets) & 15) {
     stj_set_error("%s: 16-byte aligned buffers only", who);
@@ -572,17 +667,33 @@ static int df_launch(const char* who, const uint8_t* Q, void* work, uint8_t* out
   const int HW = H * W;
   if (level == 1) hipLaunchKernelGGL(deflate_encode_kernel, dim3((unsigned)nseg), dim3(DF_NT), 0, stream, Q, slots, table, HW, nso, nsf);
   else hipLaunchKernelGGL(deflate_encode_dyn_kernel, dim3((unsigned)nseg), dim3(DF_NT), 0, stream, Q, slots, table, HW, nso, nsf);
-  hipLaunchKernelGGL(deflate_offsets_kernel, dim3(1), dim3(1024), 0, stream, table, out, offsets, B * 24, HW, nso, nsf);
+  if (framed) hipLaunchKernelGGL(deflate_offsets_framed_kernel, dim3(1), dim3(1024), 0, stream, table, out, offsets, B * 24, HW, nso, nsf, tags);
+  else hipLaunchKernelGGL(deflate_offsets_kernel, dim3(1), dim3(1024), 0, stream, table, out, offsets, B * 24, HW, nso, nsf);
   hipLaunchKernelGGL(deflate_pack_kernel, dim3((unsigned)nseg), dim3(256), 0, stream, (const uint8_t*)slots, (const uint32_t*)table,
                      (const uint32_t*)offsets, out, HW, nso, nsf);
   return stj_check_launch(who);
 }
 
 extern "C" int stj_compress_waypoints(const uint8_t* Q, void* work, uint8_t* out, uint32_t* offsets, int B, int Tn, int H, int W, hipStream_t stream) {
-  return df_launch("stj_compress_waypoints", Q, work, out, offsets, B, Tn, H, W, 1, stream);
+  return df_launch("stj_compress_waypoints", Q, work, out, offsets, B, Tn, H, W, 1, false, 0u, stream);
 }
 
 extern "C" int stj_compress_waypoints_level(const uint8_t* Q, void* work, uint8_t* out, uint32_t* offsets, int B, int Tn, int H, int W, int level,
                                             hipStream_t stream) {
-  return df_launch("stj_compress_waypoints_level", Q, work, out, offsets, B, Tn, H, W, level, stream);
+  return df_launch("stj_compress_waypoints_level", Q, work, out, offsets, B, Tn, H, W, level, false, 0u, stream);
+}
+
+extern "C" int stj_compress_framed_sizes(int B, int Tn, int H, int W, long long* work_bytes, long long* out_capacity, long long* table_words) {
+  long long nseg, cap; int nso, nsf;
+  const int rc = df_shape("stj_compress_framed_sizes", B, Tn, H, W, true, &nseg, &cap, &nso, &nsf);
+  if (rc != STJ_OK) return rc;
+  *work_bytes = df_table_bytes(nseg) + nseg * DF_SLOT;
+  *out_capacity = (cap + 15) / 16 * 16;
+  *table_words = 6ll * B * Tn + B + 1;
+  return STJ_OK;
+}
+
+extern "C" int stj_compress_waypoints_framed(const uint8_t* Q, void* work, uint8_t* out, uint32_t* table, int B, int Tn, int H, int W, int level,
+                                             uint32_t tags, hipStream_t stream) {
+  return df_launch("stj_compress_waypoints_framed", Q, work, out, table, B, Tn, H, W, level, true, tags, stream);
 }

@@ -127,7 +127,8 @@ class GraphedForward:
     (the challenge format's bytes: 4 per cell and waypoint instead of 16 to bring to the host; submission.ResultDrain does that).
     With compressed=True as well the captured forward is model.predict_compressed and the result a submission.CompressedWaypoints over
     static memory: the zlib strings, of which ResultDrain brings only the bytes they really have (compress_level=2: a dynamic Huffman
-    code per segment, streams about half the size on sparse planes).
+    code per segment, streams about half the size on sparse planes).  framed=True on top: a submission.FramedWaypoints, the streams
+    inside their protobuf framing, for submission.SubmissionWriter.
 
     pipeline_agents=True: the agent branch (trajNet: ~30 dependent launches of a few microseconds that a replayed graph starts only when
     the raster encoder is through -- 0.3 of the 6.3 ms B = 32 step with nothing beside them, profiles/r05_c_timeline_infer_b32_f16.txt) is
@@ -138,12 +139,15 @@ class GraphedForward:
     measured 1.3 % SLOWER in three same-box pairs, 5333 / 5118 / 5333 vs 5390 / 5206 / 5412 scenes/s: where those launches sit decides when the
     executor starts the other branches, DESIGN 4e.  Not kept.)"""
 
-    def __init__(self, model, batch, warmup=2, pipeline_agents=False, quantized=False, compressed=False, compress_level=1):
+    def __init__(self, model, batch, warmup=2, pipeline_agents=False, quantized=False, compressed=False, compress_level=1, framed=False):
         if compressed and not quantized:
             raise ValueError('GraphedForward: compressed=True compresses the quantised output: pass quantized=True with it')
         if compress_level not in (1, 2):
             raise ValueError(f'GraphedForward: compress_level 1 or 2, got {compress_level!r}')
+        if framed and not compressed:
+            raise ValueError('GraphedForward: framed=True frames the compressed streams: pass compressed=True with it')
         self.compress_level = compress_level
+        self.framed = framed
         self.model = model
         self.quantized = quantized
         self.compressed = compressed
@@ -185,7 +189,7 @@ class GraphedForward:
         x = self.static
         if self.compressed:
             return self.model.predict_compressed(x['ogm'], x['map_img'], obs=x['obs'], occ=x['occ'], mapt=None, flow=x['flow'],
-                                                 level=self.compress_level)
+                                                 level=self.compress_level, framed=self.framed)
         if self.quantized:
             return self.model.predict_quantized(x['ogm'], x['map_img'], obs=x['obs'], occ=x['occ'], mapt=None, flow=x['flow'])
         return self.model(x['ogm'], x['map_img'], training=False, obs=x['obs'], occ=x['occ'], mapt=None, flow=x['flow'])

@@ -848,14 +848,14 @@ class STrajNet:
                 return QuantizedWaypoints(out, H, H)
             return quantize_waypoints(out)
 
-    def predict_compressed(self, ogm, map_img, obs=None, occ=None, mapt=None, flow=None, out=None, level=1):
+    def predict_compressed(self, ogm, map_img, obs=None, occ=None, mapt=None, flow=None, out=None, level=1, framed=False):
         """predict_quantized followed by submission.compress_waypoints: the result as the challenge format's zlib strings, compressed on
         the device (submission.CompressedWaypoints; `out`: one to write into; `level`: 1 the fixed Huffman code, 2 a dynamic code per
         segment, smaller streams)."""
         from .submission import compress_waypoints
         if level not in (1, 2):
             raise ValueError(f'predict_compressed: level 1 or 2, got {level!r}')
-        return compress_waypoints(self.predict_quantized(ogm, map_img, obs=obs, occ=occ, mapt=mapt, flow=flow), out=out, level=level)
+        return compress_waypoints(self.predict_quantized(ogm, map_img, obs=obs, occ=occ, mapt=mapt, flow=flow), out=out, level=level, framed=framed)
 
     def call(self, ogm, map_img, training=True, obs=None, occ=None, mapt=None, flow=None, dense_vec=None, dense_map=None):
         """STrajNet.call (modules.py:815-839).  mapt is ignored (actor_only=True), as in the reference."""

@@ -11,8 +11,10 @@ the logits (stj_outconv_pair_gather_q; STrajNet.predict_quantized picks).  Resul
 replaying thread.  Compression: either host work (zlib: QuantizedWaypoints.compressed / compress_batch, zlib's own sizes) or on the
 device (compress_waypoints, stj_compress_waypoints: one zlib stream per plane, run-length DEFLATE with the fixed Huffman code, or at
 level 2 with a dynamic Huffman code per segment, in the format `compress_reference` states; larger streams than zlib's default, about
-zlib level 1's at level 2, no host work, and only the streams cross to the host).  `quantize_reference` and
-`compress_reference` are the only CPU code paths here.
+zlib level 1's at level 2, no host work, and only the streams cross to the host).  With framed=True the device also
+frames the streams as protobuf fields (FramedWaypoints), and SubmissionWriter turns drained batches into the challenge's
+ChallengeSubmission file, one slice per scene.  `quantize_reference`, `compress_reference`, `frame_reference`, `submission_reference`
+and `parse_submission` are the only CPU code paths here.
 
 dequantize() loses at most 1/510 in probability and 0.5 per flow component (flow beyond [-128, 127] is clipped, as in the format).
 """
@@ -433,17 +435,311 @@ class CompressedWaypoints:
         return [tuple(raw[cut[3 * k + i]:cut[3 * k + i + 1]] for i in range(3)) for k in range(self.Tn)]
 
 
-def compress_waypoints(qw, out=None, level=1):
+# ---------------------------------------------------------------------------------------------------- submission files
+# The reference's inference.py ends in one ChallengeSubmission protobuf per test shard (inference.py:186-252): a few header strings and
+# one ScenarioPrediction per scene, its id and eight Waypoint messages of three zlib strings.  Every field here is length-delimited
+# (wire type 2): tag byte (field number << 3 | 2), varint(length), payload.
+#
+# The field numbers, in ONE table; everything (the device call's tag bytes, the references, the parser, the writer, the tests) reads
+# them from here.  They are as recalled from the public occupancy_flow_submission.proto of the Waymo Open Dataset; that file was not at
+# hand when this was written and the numbers have NOT been checked against it -- a correction is one line here.
+SUBMISSION_SCHEMA = {
+    'Waypoint': {'observed_vehicles_occupancy': 1, 'occluded_vehicles_occupancy': 2, 'all_vehicles_flow': 3},
+    'ScenarioPrediction': {'scenario_id': 1, 'waypoints': 2},
+    'ChallengeSubmission': {'account_name': 1, 'unique_method_name': 2, 'authors': 3, 'affiliation': 4, 'description': 5,
+                            'method_link': 6, 'scenario_predictions': 7},
+}
+WAYPOINT_FIELDS = ('observed_vehicles_occupancy', 'occluded_vehicles_occupancy', 'all_vehicles_flow')       # the order (obs, occ, flow)
+NUM_SHARDS = 150
+
+
+def _tag(message, field):
+    n = SUBMISSION_SCHEMA[message][field]
+    if not 1 <= n <= 15:
+        raise ValueError(f'SUBMISSION_SCHEMA: {message}.{field} = {n}: one-byte tags (field numbers 1..15) only')
+    return n << 3 | 2
+
+
+def frame_tags():
+    """The four tag bytes of a scene's block as stj_compress_waypoints_framed takes them: tag_wp | tag_obs << 8 | tag_occ << 16 |
+    tag_flow << 24."""
+    t = [_tag('ScenarioPrediction', 'waypoints')] + [_tag('Waypoint', f) for f in WAYPOINT_FIELDS]
+    return t[0] | t[1] << 8 | t[2] << 16 | t[3] << 24
+
+
+def pb_varint(v):
+    """A non-negative integer below 2^64 as a base-128 varint."""
+    v = int(v)
+    if not 0 <= v < 1 << 64:
+        raise ValueError(f'pb_varint: {v} is not a uint64')
+    out = bytearray()
+    while v >= 0x80:
+        out.append(v & 0x7f | 0x80)
+        v >>= 7
+    out.append(v)
+    return bytes(out)
+
+
+def _field(tag, payload):
+    return bytes([tag]) + pb_varint(len(payload)) + payload
+
+
+def frame_reference(streams):
+    """A scene's block -- the wire form of its `repeated Waypoint waypoints` -- from a `streams(b)`-shaped list of (obs, occ, flow) byte
+    strings: what stj_compress_waypoints_framed leaves in the packed buffer, byte for byte (the rules for C: csrc/frame.h).  CPU."""
+    tw = _tag('ScenarioPrediction', 'waypoints')
+    tf = [_tag('Waypoint', f) for f in WAYPOINT_FIELDS]
+    return b''.join(_field(tw, b''.join(_field(t, bytes(s)) for t, s in zip(tf, wp))) for wp in streams)
+
+
+def _as_bytes(s):
+    return s.encode('utf-8') if isinstance(s, str) else bytes(s)
+
+
+def _header_bytes(header):
+    """The ChallengeSubmission's string fields in field-number order; a list or tuple is a repeated field, None is left out."""
+    out = []
+    for name, _ in sorted(SUBMISSION_SCHEMA['ChallengeSubmission'].items(), key=lambda kv: kv[1]):
+        v = header.get(name) if name != 'scenario_predictions' else None
+        if v is None:
+            continue
+        for s in (v if isinstance(v, (list, tuple)) else (v,)):
+            out.append(_field(_tag('ChallengeSubmission', name), _as_bytes(s)))
+    unknown = set(header) - set(SUBMISSION_SCHEMA['ChallengeSubmission']) | ({'scenario_predictions'} & set(header))
+    if unknown:
+        raise ValueError(f'submission header: unknown fields {sorted(unknown)}')
+    return b''.join(out)
+
+
+def _scene_prefix(sid, block_len):
+    """What stands in front of a scene's block: tag7 varint(n) tag1 varint(len(id)) id."""
+    idf = _field(_tag('ScenarioPrediction', 'scenario_id'), _as_bytes(sid))
+    return bytes([_tag('ChallengeSubmission', 'scenario_predictions')]) + pb_varint(len(idf) + block_len) + idf
+
+
+def submission_reference(header, ids, scenes):
+    """The whole file: `header` a dict of ChallengeSubmission's string fields (authors: a list), ids the scenario ids, scenes a
+    `streams(b)`-shaped list per id.  Pure Python, the order protobuf's own serialiser writes.  CPU."""
+    if len(ids) != len(scenes):
+        raise ValueError('submission_reference: one id per scene')
+    out = [_header_bytes(header)]
+    for sid, streams in zip(ids, scenes):
+        block = frame_reference(streams)
+        out += [_scene_prefix(sid, len(block)), block]
+    return b''.join(out)
+
+
+def _pb_fields(buf, lo, hi):
+    """(field number, wire type, value) of every field of the message buf[lo:hi]; a length-delimited value is a (lo, hi) pair."""
+    def varint(p):
+        v = sh = 0
+        while True:
+            if p >= hi or sh > 63:
+                raise ValueError('parse_submission: bad varint')
+            c = buf[p]
+            p += 1
+            v |= (c & 0x7f) << sh
+            sh += 7
+            if c < 0x80:
+                return v, p
+    p = lo
+    while p < hi:
+        key, p = varint(p)
+        num, wt = key >> 3, key & 7
+        if wt == 0:
+            val, p = varint(p)
+        elif wt == 2:
+            n, p = varint(p)
+            val, p = (p, p + n), p + n
+        elif wt in (1, 5):
+            val, p = None, p + (8 if wt == 1 else 4)
+        else:
+            raise ValueError(f'parse_submission: wire type {wt}')
+        if p > hi or num == 0:
+            raise ValueError('parse_submission: truncated message')
+        yield num, wt, val
+
+
+def parse_submission(data):
+    """A hand-written reader of the wire format: (header, ids, scenes) of a ChallengeSubmission file -- header: the string fields present
+    (authors a list), ids: the scenario ids as str, scenes: per id a list of (obs, occ, flow) byte strings per waypoint (a field a
+    waypoint lacks is b'').  Fields the schema does not name are skipped.  CPU."""
+    buf = bytes(data)
+    top = {n: k for k, n in SUBMISSION_SCHEMA['ChallengeSubmission'].items()}
+    sp, wf = SUBMISSION_SCHEMA['ScenarioPrediction'], [SUBMISSION_SCHEMA['Waypoint'][f] for f in WAYPOINT_FIELDS]
+    header, ids, scenes = {}, [], []
+    for num, wt, val in _pb_fields(buf, 0, len(buf)):
+        name = top.get(num)
+        if name is None or wt != 2:
+            continue
+        if name != 'scenario_predictions':
+            s = buf[val[0]:val[1]].decode('utf-8')
+            if name == 'authors':
+                header.setdefault(name, []).append(s)
+            else:
+                header[name] = s
+            continue
+        sid, wps = '', []
+        for n2, w2, v2 in _pb_fields(buf, *val):
+            if w2 != 2:
+                continue
+            if n2 == sp['scenario_id']:
+                sid = buf[v2[0]:v2[1]].decode('utf-8')
+            elif n2 == sp['waypoints']:
+                wp = [b'', b'', b'']
+                for n3, w3, v3 in _pb_fields(buf, *v2):
+                    if w3 == 2 and n3 in wf:
+                        wp[wf.index(n3)] = buf[v3[0]:v3[1]]
+                wps.append(tuple(wp))
+        ids.append(sid)
+        scenes.append(wps)
+    return header, ids, scenes
+
+
+def compress_framed_sizes(B, H, W, Tn=NUM_WAYPOINTS):
+    """(workspace bytes, capacity of the packed buffer, words of the table) of stj_compress_waypoints_framed."""
+    v = [ctypes.c_longlong(0) for _ in range(3)]
+    _host_call('stj_compress_framed_sizes', B, Tn, H, W, *(ctypes.c_void_p(ctypes.addressof(x)) for x in v))
+    return tuple(x.value for x in v)
+
+
+class FramedWaypoints:
+    """The zlib streams of a batch inside their protobuf framing, packed: scene b's block, buf[scene[b]:scene[b + 1]], is the wire form of
+    its `repeated Waypoint waypoints` (frame_reference), ready to go into a ScenarioPrediction behind the id.  `table` [6*B*Tn + B + 1]
+    (int32 storage, read as uint32; one allocation, so that one small copy brings it): the start of every stream's zlib bytes [3*B*Tn],
+    every stream's length [3*B*Tn], the scene starts [B + 1] whose last entry is the total.  On the device `buf` has the capacity of the
+    worst case; `work` is the kernels' scratch (compress_waypoints(out=, framed=True) writes the object again)."""
+
+    def __init__(self, buf, table, B, Tn=NUM_WAYPOINTS, work=None):
+        if buf.dtype != torch.uint8 or buf.dim() != 1 or table.dim() != 1 or table.numel() != 6 * B * Tn + B + 1 or table.dtype != torch.int32:
+            raise ValueError(f'FramedWaypoints: expected a uint8 [n] buffer and an int32 [{6 * B * Tn + B + 1}] table, got '
+                             f'{buf.dtype} {tuple(buf.shape)}, {table.dtype} {tuple(table.shape)}')
+        self.buf, self.table, self.B, self.Tn, self.work = buf, table, B, Tn, work
+
+    @classmethod
+    def empty(cls, B, H, W, device, Tn=NUM_WAYPOINTS):
+        """Device memory for the framed streams of a [B, 4*Tn*H*W] QuantizedWaypoints."""
+        work, cap, words = compress_framed_sizes(B, H, W, Tn)
+        return cls(torch.empty(cap, dtype=torch.uint8, device=device), torch.empty(words, dtype=torch.int32, device=device), B, Tn,
+                   work=torch.empty(work, dtype=torch.uint8, device=device))
+
+    @property
+    def batch(self):
+        return self.B
+
+    def _host_table(self):
+        return self.table.cpu().numpy().view(np.uint32).astype(np.int64)
+
+    def scene_starts(self):
+        """[B + 1] host int64: scene b's block is buf[s[b]:s[b + 1]]."""
+        return self._host_table()[6 * self.B * self.Tn:]
+
+    @property
+    def nbytes(self):
+        """Total size of the framed blocks (a device object is asked: one small synchronous copy)."""
+        return int(self._host_table()[-1])
+
+    def cpu(self):
+        """Synchronous copy to host memory: the table, then the table[-1] bytes that are blocks."""
+        if not self.buf.is_cuda:
+            return self
+        tab = self.table.cpu()
+        total = int(tab.numpy().view(np.uint32)[-1])
+        return FramedWaypoints(self.buf[:total].cpu(), tab, self.B, self.Tn)
+
+    def scene_message(self, b):
+        """Scene b's framed block as bytes."""
+        s = self.scene_starts()
+        return self.buf[int(s[b]):int(s[b + 1])].cpu().numpy().tobytes()
+
+    def streams(self, b):
+        """Scene b: a list of Tn (obs, occ, flow) zlib strings, the shape of CompressedWaypoints.streams(b)."""
+        t, n, m = self._host_table(), 3 * self.B * self.Tn, 3 * self.Tn
+        lo, hi = int(t[2 * n + b]), int(t[2 * n + b + 1])
+        raw = self.buf[lo:hi].cpu().numpy().tobytes()
+        cut = [(int(t[m * b + j]) - lo, int(t[m * b + j]) - lo + int(t[n + m * b + j])) for j in range(m)]
+        return [tuple(raw[cut[3 * k + i][0]:cut[3 * k + i][1]] for i in range(3)) for k in range(self.Tn)]
+
+
+class SubmissionWriter:
+    """One shard's ChallengeSubmission file from host FramedWaypoints (what ResultDrain.take() or FramedWaypoints.cpu() gives):
+
+        with open(os.path.join(save_dir, SubmissionWriter.shard_name(test_shard_path)), 'wb') as f:
+            w = SubmissionWriter(f)
+            for ids in ...:
+                w.add_batch(drain.take(), ids)
+            w.close()
+
+    The header fields are the ones the reference sets, with its (empty) values as defaults (inference.py:216-226); `affiliation` is in
+    the schema, the reference does not set it, and it is not written.  Per scene the writer appends tag7 varint(n) tag1 varint(len(id)) id
+    and ONE slice of the batch's buffer -- no per-stream work.  path_or_file: a path (opened and closed here) or a binary file object
+    (flushed, not closed)."""
+
+    def __init__(self, path_or_file, account_name='', unique_method_name='', authors=('',), description='', method_link=''):
+        self._own = isinstance(path_or_file, (str, os.PathLike))
+        self.f = open(path_or_file, 'wb') if self._own else path_or_file
+        self.scenes = 0
+        self.f.write(_header_bytes(dict(account_name=account_name, unique_method_name=unique_method_name, authors=list(authors),
+                                        description=description, method_link=method_link)))
+
+    def add_batch(self, framed, ids):
+        """The first len(ids) <= B scenes of a HOST FramedWaypoints under these ids (a last short batch: fewer ids than scenes)."""
+        if framed.buf.is_cuda:
+            raise ValueError('SubmissionWriter.add_batch: a host FramedWaypoints (ResultDrain.take() or .cpu())')
+        if len(ids) > framed.B:
+            raise ValueError(f'SubmissionWriter.add_batch: {len(ids)} ids for a batch of {framed.B}')
+        s = framed.scene_starts()
+        mem = memoryview(framed.buf.numpy())
+        for b, sid in enumerate(ids):
+            lo, hi = int(s[b]), int(s[b + 1])
+            self.f.write(_scene_prefix(sid, hi - lo))
+            self.f.write(mem[lo:hi])
+        self.scenes += len(ids)
+
+    def close(self):
+        if self.f is not None:
+            self.f.close() if self._own else self.f.flush()
+            self.f = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @staticmethod
+    def shard_name(test_shard_path):
+        """The submission file's name for a test shard (inference.py:240-244): the shard's first five characters are its number."""
+        base = os.path.basename(test_shard_path)
+        if 'new.tfrecords' not in base:
+            raise ValueError(f'SubmissionWriter.shard_name: {base!r} is not a test shard (no "new.tfrecords" in its name)')
+        return f'occupancy_flow_submission.binproto-{base[:5]}-of-{NUM_SHARDS:05d}'
+
+
+def compress_waypoints(qw, out=None, level=1, framed=False):
     """A device QuantizedWaypoints -> CompressedWaypoints (stj_compress_waypoints: no host synchronisation, no allocation with `out`
     given -- a CompressedWaypoints.empty of the same shape, written in place -- so the call can be captured in a graph).  level 1: the
     fixed Huffman code; level 2: per segment the shortest of stored, fixed and a dynamic Huffman code of its own
-    (stj_compress_waypoints_level; compress_reference(level=2)): smaller streams from the same three launches' worth of work."""
+    (stj_compress_waypoints_level; compress_reference(level=2)): smaller streams from the same three launches' worth of work.
+    framed=True: -> FramedWaypoints (stj_compress_waypoints_framed; `out`: a FramedWaypoints.empty): the same streams inside their
+    protobuf framing, the same number of launches."""
     if level not in (1, 2):
         raise ValueError(f'compress_waypoints: level 1 or 2, got {level!r}')
     if not qw.buf.is_cuda:
         raise RuntimeError('compress_waypoints: CUDA (ROCm) buffers only: the HIP path has no CPU fallback (CPU: compress_reference, '
                            'or zlib through QuantizedWaypoints.compressed)')
     B = qw.batch
+    if framed:
+        if out is None:
+            out = FramedWaypoints.empty(B, qw.H, qw.W, qw.buf.device, qw.Tn)
+        else:
+            work, cap, words = compress_framed_sizes(B, qw.H, qw.W, qw.Tn)
+            if (not isinstance(out, FramedWaypoints) or out.work is None or not out.buf.is_cuda or out.B != B or out.Tn != qw.Tn
+                    or out.buf.numel() < cap or out.work.numel() < work or out.buf.device != qw.buf.device):
+                raise ValueError('compress_waypoints: `out` must be a FramedWaypoints.empty() of the same shape on the same device')
+        call('stj_compress_waypoints_framed', _p(qw.buf), _p(out.work), _p(out.buf), _p(out.table), B, qw.Tn, qw.H, qw.W, level,
+             frame_tags(), _st())
+        return out
     if out is None:
         out = CompressedWaypoints.empty(B, qw.H, qw.W, qw.buf.device, qw.Tn)
     else:
@@ -461,7 +757,8 @@ def compress_waypoints(qw, out=None, level=1):
 class ResultDrain:
     """The output-side twin of data.HostFeed: brings the static quantised buffer of a GraphedForward(quantized=True) to pinned host
     memory, one batch per replay, without stalling the replaying thread (or the CompressedWaypoints of a GraphedForward(quantized=True,
-    compressed=True): then the worker brings the offsets table first and only the offsets[-1] bytes that are streams):
+    compressed=True), or the FramedWaypoints of one with framed=True as well: then the worker brings the offsets table first and only the
+    offsets[-1] bytes that are streams):
 
         drain = ResultDrain(gf.out)
         for batch in batches:
@@ -487,10 +784,12 @@ class ResultDrain:
         self.depth, self.chunk = int(depth), int(chunk_bytes)
         self.stage = [torch.empty_like(qw.buf) for _ in range(self.depth)]
         self.ring = [torch.empty(qw.buf.shape, dtype=torch.uint8).pin_memory() for _ in range(self.depth)]
-        self.compressed = isinstance(qw, CompressedWaypoints)
-        if self.compressed:       # + the offsets table; the worker reads it first and brings only offsets[-1] bytes of the buffer
-            self.stage_off = [torch.empty_like(qw.offsets) for _ in range(self.depth)]
-            self.ring_off = [torch.empty(qw.offsets.shape, dtype=torch.int32).pin_memory() for _ in range(self.depth)]
+        self.framed = isinstance(qw, FramedWaypoints)
+        self.compressed = self.framed or isinstance(qw, CompressedWaypoints)
+        if self.compressed:       # + the offsets table (framed: the table); the worker reads it first and brings only [-1] bytes of the buffer
+            side = self._side()
+            self.stage_off = [torch.empty_like(side) for _ in range(self.depth)]
+            self.ring_off = [torch.empty(side.shape, dtype=torch.int32).pin_memory() for _ in range(self.depth)]
             self._total = [0] * self.depth
         self.copy = _copy_stream(self.dev)
         self._done = [torch.cuda.Event() for _ in range(self.depth)]      # slot i's host copy has arrived
@@ -503,6 +802,9 @@ class ResultDrain:
         self._err = None
         self._thread = threading.Thread(target=self._run, daemon=True)
         self._thread.start()
+
+    def _side(self):
+        return self.src.table if self.framed else self.src.offsets
 
     def _run(self):
         torch.cuda.set_device(self.dev)
@@ -539,7 +841,7 @@ class ResultDrain:
             main.wait_event(self._done[slot])        # (taken already, so recorded: the slot's previous host copy has left the staging buffer)
         self.stage[slot].copy_(self.src.buf, non_blocking=True)
         if self.compressed:
-            self.stage_off[slot].copy_(self.src.offsets, non_blocking=True)
+            self.stage_off[slot].copy_(self._side(), non_blocking=True)
         self._enq[slot].clear()
         self._ready[slot].record(main)
         self._n_sub += 1
@@ -548,7 +850,8 @@ class ResultDrain:
             self._cv.notify()
 
     def take(self):
-        """The oldest submitted batch as a host QuantizedWaypoints (CompressedWaypoints for such a source), a view of ring memory."""
+        """The oldest submitted batch as a host QuantizedWaypoints (CompressedWaypoints, FramedWaypoints for such a source), a view of ring
+        memory."""
         if self._n_take >= self._n_sub:
             raise RuntimeError('ResultDrain: nothing submitted')
         slot = self._n_take % self.depth
@@ -558,6 +861,8 @@ class ResultDrain:
             raise e
         self._done[slot].synchronize()
         self._n_take += 1
+        if self.framed:
+            return FramedWaypoints(self.ring[slot][:self._total[slot]], self.ring_off[slot], self.src.B, self.src.Tn)
         if self.compressed:
             return CompressedWaypoints(self.ring[slot][:self._total[slot]], self.ring_off[slot], self.src.B, self.src.Tn)
         return QuantizedWaypoints(self.ring[slot], self.src.H, self.src.W, self.src.Tn)

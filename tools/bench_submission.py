@@ -4,7 +4,9 @@
   --mode rows   scenes/s for (a) no read-back (bench.py --infer's figure), (b) the float32 output copied to pinned memory each step,
                 (c) quantised output + ResultDrain, (d) as (c) plus zlib compression of every scene on 16 threads, (e) the graph that
                 also compresses on the device (GraphedForward(quantized=True, compressed=True, compress_level=--level)) + ResultDrain,
-                no host zlib; bytes per scene of (d) and (e) side by side
+                no host zlib; bytes per scene of (d) and (e) side by side; (f) the graph that also frames the streams on the device
+                (framed=True) + ResultDrain + SubmissionWriter into a BytesIO (rewound per batch): a submission file's bytes; (g) as
+                (e), each scene framed on the host with frame_reference and written the same way.  --rows picks a subset.
   --mode ab     GraphedForward(quantized=True) with the quantising gather (stj_outconv_pair_gather_q) against the same graph built from
                 stj_outconv_pair_gather + stj_quantize_waypoints, alternating, --pairs times; each build is timed TWICE in a row per
                 visit, so the spread of repeated runs of the same build is measured in the same call
@@ -12,7 +14,10 @@
   --sparse      (instead of a mode) random weights give noise-like planes, which the device-side compressor mostly stores; this fills a
                 static quantised buffer ONCE with synthetic sparse planes (seeded blobs on a zero background) and times
                 stj_compress_waypoints at --level (captured) + ResultDrain alone against host compress_batch of the same bytes on --threads threads.
-                With --trace-only: a few replays of the captured compression and nothing else, for a kernel trace.
+                With --trace-only: a few replays of the captured compression, unframed then framed, and nothing else, for a kernel
+                trace.  With --mode ab: the device entry pair, stj_compress_waypoints_framed against stj_compress_waypoints_level on
+                the same Q and level, each captured; device events around --steps replays; per round the framed chain once and the
+                unframed one twice, --pairs rounds alternating.
 
 Every timing is a host clock around `--steps` replays that end in a device synchronise, after `--warmup` replays, profiler off.
 One JSON line per mode on stdout."""
@@ -36,12 +41,15 @@ ap.add_argument('--chunk-bytes', type=int, default=3 << 19)
 ap.add_argument('--sparse', action='store_true')
 ap.add_argument('--noise', action='store_true', help='with --sparse: uniformly random planes instead (the stored fallback everywhere)')
 ap.add_argument('--trace-only', action='store_true')
+ap.add_argument('--rows', default='abcdefg', help='--mode rows: the rows to measure')
 ap.add_argument('--level', type=int, default=1, choices=[1, 2], help='compression level of row (e) and of --sparse: 1 fixed, 2 dynamic Huffman code')
 a = ap.parse_args()
 
 import bench
+import io
 from strajnet_amd import (STrajNet, ResultDrain, compress_batch, compression_pool, QuantizedWaypoints, CompressedWaypoints,
-                          compress_waypoints)
+                          compress_waypoints, FramedWaypoints, SubmissionWriter, frame_reference)
+from strajnet_amd.submission import _scene_prefix
 from strajnet_amd.graph import GraphedForward
 
 assert torch.cuda.is_available(), 'bench_submission.py needs a GPU'
@@ -90,12 +98,47 @@ if a.sparse:
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
         compress_waypoints(qw, out=cw, level=a.level)
-    if a.trace_only:
-        for _ in range(10):
-            g.replay()
+    if a.trace_only or a.mode == 'ab':
+        fw = FramedWaypoints.empty(B, H, H, dev)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            compress_waypoints(qw, out=fw, level=a.level, framed=True)
+        torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        print(json.dumps({'mode': 'sparse-trace', 'batch': B, 'level': a.level, 'replays': 10 + 1, 'noise': a.noise, 'input_bytes': qw.buf.numel(),
-                          'stream_bytes': cw.nbytes}), flush=True)
+        gfr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gfr):
+            compress_waypoints(qw, out=fw, level=a.level, framed=True)
+    if a.trace_only:
+        for gr in (g, gfr):
+            for _ in range(10):
+                gr.replay()
+            torch.cuda.synchronize()
+        print(json.dumps({'mode': 'sparse-trace', 'batch': B, 'level': a.level, 'replays_per_graph': 10 + 1, 'noise': a.noise,
+                          'input_bytes': qw.buf.numel(), 'stream_bytes': cw.nbytes, 'framed_bytes': fw.nbytes}), flush=True)
+        sys.exit(0)
+    if a.mode == 'ab':
+        def ms(gr):
+            for _ in range(a.warmup):
+                gr.replay()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.steps):
+                gr.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / a.steps
+        assert fw.streams(B - 1) == cw.streams(B - 1)
+        rounds = [{'framed': [round(ms(gfr), 5)], 'unframed': [round(ms(g), 5) for _ in range(2)]} for _ in range(a.pairs)]
+        un = sorted(t for r in rounds for t in r['unframed'])
+        fr = sorted(t for r in rounds for t in r['framed'])
+        med = lambda v: (v[(len(v) - 1) // 2] + v[len(v) // 2]) / 2
+        spread = (un[-1] - un[0]) / un[0]
+        ratio = med(fr) / med(un)
+        print(json.dumps({'mode': 'sparse-ab', 'noise': a.noise, 'batch': B, 'level': a.level, 'steps': a.steps, 'warmup': a.warmup,
+                          'unit': 'ms per captured chain', 'rounds': rounds, 'framed_median': round(med(fr), 5),
+                          'unframed_median': round(med(un), 5), 'unframed_spread': round(spread, 4), 'ratio': round(ratio, 4),
+                          'gate': '<= 1.02 + spread', 'within_gate': ratio <= 1.02 + spread, 'stream_bytes': cw.nbytes,
+                          'framed_bytes': fw.nbytes}), flush=True)
         sys.exit(0)
     drain = ResultDrain(cw, depth=3, chunk_bytes=a.chunk_bytes)
     pending = [0]
@@ -149,10 +192,11 @@ model = STrajNet(bench.CFG256, fg_msa=True, fg=True, large_ogm=False, dtype=torc
 x = bench.synth_batch(B, 1234, dev, 256)
 
 
-def graph(quantized, fused=True, compressed=False, level=1):
+def graph(quantized, fused=True, compressed=False, level=1, framed=False):
     model.fused_quantize = fused
     try:
-        return GraphedForward(model, x, pipeline_agents=True, quantized=quantized, compressed=compressed, compress_level=level)
+        return GraphedForward(model, x, pipeline_agents=True, quantized=quantized, compressed=compressed, compress_level=level,
+                              framed=framed)
     finally:
         model.fused_quantize = True
 
@@ -181,75 +225,109 @@ def replay(gf):
 
 if a.mode == 'rows':
     res = {}
-    gf = graph(False)
-    res['a_no_readback'] = timed(replay(gf))
-    # (b) the float32 output, stream-ordered into one pinned buffer, each step (what a user of the float output does)
-    host = torch.empty(gf.out.shape, dtype=torch.float32).pin_memory()
+    if set('ab') & set(a.rows):
+        gf = graph(False)
+        res['a_no_readback'] = timed(replay(gf))
+        # (b) the float32 output, stream-ordered into one pinned buffer, each step (what a user of the float output does)
+        host = torch.empty(gf.out.shape, dtype=torch.float32).pin_memory()
 
-    def step_b():
-        gf()
-        gf.prefetch_agents()
-        host.copy_(gf.out, non_blocking=True)
-    res['b_f32_to_pinned'] = timed(step_b)
-    res['b_bytes_per_scene'] = gf.out[0].numel() * 4
-    res['a_again'] = timed(replay(gf))
-    del gf, host
-    gq = graph(True)
-    res['q_no_readback'] = timed(replay(gq))
-    for with_zlib in (False, True):
-        drain = ResultDrain(gq.out, depth=3, chunk_bytes=a.chunk_bytes)
-        pool = compression_pool(a.threads) if with_zlib else None
-        pending = [0]
-        sizes = []
+        def step_b():
+            gf()
+            gf.prefetch_agents()
+            host.copy_(gf.out, non_blocking=True)
+        res['b_f32_to_pinned'] = timed(step_b)
+        res['b_bytes_per_scene'] = gf.out[0].numel() * 4
+        res['a_again'] = timed(replay(gf))
+        del gf, host
+    if set('cd') & set(a.rows):
+        gq = graph(True)
+        res['q_no_readback'] = timed(replay(gq))
+        for with_zlib in (False, True):
+            drain = ResultDrain(gq.out, depth=3, chunk_bytes=a.chunk_bytes)
+            pool = compression_pool(a.threads) if with_zlib else None
+            pending = [0]
+            sizes = []
 
-        def consume():
-            q = drain.take()
+            def consume():
+                q = drain.take()
+                pending[0] -= 1
+                if pool is not None:
+                    comp = compress_batch(q, pool)
+                    sizes.append(sum(len(s) for scene in comp for wp in scene for s in wp))
+
+            def step_c():
+                gq()
+                gq.prefetch_agents()
+                drain.submit()
+                pending[0] += 1
+                if pending[0] > 1:                  # the previous batch arrives (and is compressed) under this replay
+                    consume()
+
+            def finish():
+                while pending[0]:
+                    consume()
+            res['d_quantized_drain_zlib' if with_zlib else 'c_quantized_drain'] = timed(step_c, finish)
+            if with_zlib:
+                res['d_compressed_bytes_per_scene'] = sum(sizes) / len(sizes) / B
+                pool.shutdown()
+            drain.close()
+        res['c_bytes_per_scene'] = gq.out.buf.shape[1]
+        del gq
+    def drained(key, framed, write):
+        """Rows (e), (f), (g): a compressing graph + ResultDrain; write(host batch) is the host work per arrived batch."""
+        ge = graph(True, compressed=True, level=a.level, framed=framed)
+        drain = ResultDrain(ge.out, depth=3, chunk_bytes=a.chunk_bytes)
+        pending, sizes = [0], []
+
+        def consume_e():
+            h = drain.take()
+            sizes.append(h.buf.numel())
+            if write is not None:
+                write(h)
             pending[0] -= 1
-            if pool is not None:
-                comp = compress_batch(q, pool)
-                sizes.append(sum(len(s) for scene in comp for wp in scene for s in wp))
 
-        def step_c():
-            gq()
-            gq.prefetch_agents()
+        def step_e():
+            ge()
+            ge.prefetch_agents()
             drain.submit()
             pending[0] += 1
-            if pending[0] > 1:                  # the previous batch arrives (and is compressed) under this replay
-                consume()
+            if pending[0] > 1:
+                consume_e()
 
-        def finish():
+        def finish_e():
             while pending[0]:
-                consume()
-        res['d_quantized_drain_zlib' if with_zlib else 'c_quantized_drain'] = timed(step_c, finish)
-        if with_zlib:
-            res['d_compressed_bytes_per_scene'] = sum(sizes) / len(sizes) / B
-            pool.shutdown()
+                consume_e()
+        res[key] = timed(step_e, finish_e)
+        res[key[0] + '_bytes_per_scene'] = sum(sizes) / len(sizes) / B
         drain.close()
-    res['c_bytes_per_scene'] = gq.out.buf.shape[1]
-    del gq
-    ge = graph(True, compressed=True, level=a.level)
-    drain = ResultDrain(ge.out, depth=3, chunk_bytes=a.chunk_bytes)
-    pending, sizes = [0], []
+        return ge.out.nbytes
 
-    def consume_e():
-        sizes.append(drain.take().buf.numel())
-        pending[0] -= 1
+    ids = ['%016x' % (0x637f20cafde22ff8 + i) for i in range(B)]
+    sink = io.BytesIO()
 
-    def step_e():
-        ge()
-        ge.prefetch_agents()
-        drain.submit()
-        pending[0] += 1
-        if pending[0] > 1:
-            consume_e()
+    def write_framed(h):                        # (f): the writer's one slice per scene
+        sink.seek(0)
+        w = SubmissionWriter(sink)
+        w.add_batch(h, ids)
+        w.close()
 
-    def finish_e():
-        while pending[0]:
-            consume_e()
-    res['e_compressed_drain'] = timed(step_e, finish_e)
-    res['e_compressed_bytes_per_scene'] = sum(sizes) / len(sizes) / B
-    res['stream_bytes'] = ge.out.nbytes
-    drain.close()
+    def write_host_framed(h):                   # (g): 24 slices, their headers and a join per scene, on this thread
+        sink.seek(0)
+        w = SubmissionWriter(sink)
+        for b, sid in enumerate(ids):
+            blk = frame_reference(h.streams(b))
+            sink.write(_scene_prefix(sid, len(blk)))
+            sink.write(blk)
+        w.close()
+    if 'e' in a.rows:
+        res['stream_bytes'] = drained('e_compressed_drain', False, None)
+        res['e_compressed_bytes_per_scene'] = res.pop('e_bytes_per_scene')
+    if 'f' in a.rows:
+        res['framed_bytes'] = drained('f_framed_drain_writer', True, write_framed)
+        res['f_file_bytes_per_batch'] = sink.tell()
+    if 'g' in a.rows:
+        drained('g_compressed_drain_host_framing', False, write_host_framed)
+        res['g_file_bytes_per_batch'] = sink.tell()
     print(json.dumps({'mode': 'rows', 'batch': B, 'level': a.level, 'steps': a.steps, 'warmup': a.warmup, 'unit': 'scenes/s',
                       **{k: round(v, 1) for k, v in res.items()}}), flush=True)
 elif a.mode == 'ab':
