@@ -392,10 +392,13 @@ static bool ws2_launch_t(const void* X, const void* Wf, const float* bias, void*
   const int dbg = 0;      // (role-ablation mask of the kernel; profiling builds only)
   if constexpr (NF == 2) {
     // three cout groups of 32 (the 128 -> 96 layer): 1-D grid, the groups of a walker on one XCD (XCT = 3); walkers a multiple of 8
-    if (ct == 3 && ntiles >= 8) {
+    int nw = 256 / 3 / 8 * 8;                          // 80 walkers x 3 groups = 240 workgroups
+    while (nw > 8 && nw - 8 >= ntiles) nw -= 8;
+    // The straight-line movers (EXACT) drain their walker's first tile without asking whether it exists: a walker past the last tile
+    // (ntiles no multiple of 8 and below 80) would store one step of stage beyond Y.  Such a shape takes the 2-D grid, whose walkers
+    // all have a tile; the guarded movers test every tile.
+    if (ct == 3 && ntiles >= 8 && (!EXACT || nw <= ntiles)) {
       if (!stj_reserve_lds<upconv_fwd_ws2_kernel<T, KS, NF, EXACT, false, 3>>((int)lds)) return false;
-      int nw = 256 / 3 / 8 * 8;                        // 80 walkers x 3 groups = 240 workgroups
-      while (nw > 8 && nw - 8 >= ntiles) nw -= 8;
       hipLaunchKernelGGL((upconv_fwd_ws2_kernel<T, KS, NF, EXACT, false, 3>), dim3(nw * 3), dim3(512), lds, st, (const T*)X, (const T*)Wf, bias, (T*)Y, F, Hi, Wi, Cout,
                          ntiles, dbg, (const float*)nullptr);
       return true;
