@@ -478,6 +478,24 @@ int stj_outconv_bwd(const void* X, const float* W, const float* dY, void* dX, fl
                     int C, int Tn, long long y_bstride, long long y_tstride, long long y_pstride, int elu_in, void* ws,
                     long long ws_bytes, int dtype, hipStream_t stream);
 long long stj_outconv_bwd_workspace_bytes(void);   /* size of the caller-owned scratch `ws` (not zeroed; may be NULL: slower path) */
+/* What tests/test_heads_abi_gpu.py pins down for the output heads (statements and dispatch mirrors: tests/_heads_cases.py).
+ * Arguments.  stj_outconv_fwd / _bwd: H, W multiples of 16, C of 8, F >= 1, Tn >= 1 and F a multiple of Tn (a frame is split f / Tn,
+ * f % Tn), a known dtype, bwd: dW and db not NULL -- STJ_EINVAL otherwise, before any launch; C beyond the generic kernels' LDS (and, bwd,
+ * 9 C > 1024; C = 112 is the largest) is STJ_EUNSUPPORTED.  stj_outconv_pair_fwd, stj_outconv_pair_gather(_q): B < 1 or Tn < 1 is
+ * STJ_EINVAL; f32, Tn != 8, H or W no multiple of 16, C != 48 (pair), a Y / Q / Z that is not 16-byte aligned are STJ_EUNSUPPORTED.
+ * stj_upconv_fwd_head: the argument checks of stj_upconv_fwd, then STJ_EUNSUPPORTED for f32, Cin != 96, Cout != 48, Hi % 8, Wi % 16.  A
+ * refused call writes nothing.
+ * Kernels.  stj_outconv_fwd: bf16 / fp16 with C = 48, even y_bstride, y_tstride and y_pstride and an 8-byte aligned Y take the MFMA kernel
+ * (its stores are float2 at Y + b*y_bstride + t*y_tstride + p*y_pstride), at most 768 workgroups walking the tiles; every other legal call
+ * the generic one, a workgroup per tile.  stj_outconv_bwd: the same conditions on dY, bf16 only, and a ws of at least
+ * stj_outconv_bwd_workspace_bytes() take the MFMA kernel; fp16, f32, ws == NULL or shorter, an odd stride or a 4-byte aligned dY the
+ * generic one (at most 1024 workgroups).  The frame order is read from y_bstride < y_tstride (t-major callers hand Tn = B and the two
+ * strides exchanged); any Tn and any whole number of scenes is legal, Tn = 8 with a multiple of 8 spatial tiles is dealt to the XCDs
+ * per tile.
+ * Semantics.  A head writes the two floats of its own (b, t, pixel) positions and no other byte of Y: the other 30 channels of the
+ * interleaved [B,H,W,32] tensor keep what they held.  dW and db are "+=" into what the buffers hold; the contents of ws are irrelevant on
+ * entry and undefined afterwards.  Z channels 18 and 19 are written as +0 by stj_upconv_fwd_head and never read by the gather: its Y and
+ * Q do not depend on them.  Q of stj_outconv_pair_gather_q equals stj_quantize_waypoints of stj_outconv_pair_gather's Y byte for byte. */
 /* PatchEmbed Conv2D k=4 s=4 VALID as im2col (+ f32->T cast, + stride-2 pick of ogm[...,0]; modules.py:430-431,572). */
 int stj_im2col_patch(const float* src, void* dst, int B, int H, int W, int Cin, long long pix_stride, int ch_stride,
                      int dtype, hipStream_t stream);

@@ -843,9 +843,16 @@ __global__ __launch_bounds__(256) void outconv_bwd_kernel(const T* X, const floa
   if ((tid & 63) == 0) { atomicAdd(db, b0); atomicAdd(db + 1, b1); }
 }
 
+// F frames split as (f / Tn, f % Tn) by every kernel of the family (and by oc_decode through F / Tn): F must be a whole number of groups
+static int outconv_check(const char* who, int F, int Hh, int Ww, int C, int Tn) {
+  if (Hh % OC_T || Ww % OC_T || C % 8) { stj_set_error("outconv: H,W must be multiples of 16 and C of 8"); return STJ_EINVAL; }
+  if (F < 1 || Hh < 1 || Ww < 1 || C < 1) { stj_set_error("%s: empty problem (F=%d H=%d W=%d C=%d)", who, F, Hh, Ww, C); return STJ_EINVAL; }
+  if (Tn < 1 || F % Tn) { stj_set_error("%s: F=%d must be a positive multiple of Tn=%d", who, F, Tn); return STJ_EINVAL; }
+  return STJ_OK;
+}
 extern "C" int stj_outconv_fwd(const void* X, const float* W, const float* bias, float* Y, int F, int Hh, int Ww, int C, int Tn,
                                long long y_bstride, long long y_tstride, long long y_pstride, int dtype, hipStream_t stream) {
-  if (Hh % OC_T || Ww % OC_T || C % 8) { stj_set_error("outconv: H,W must be multiples of 16 and C of 8"); return STJ_EINVAL; }
+  if (int e = outconv_check("stj_outconv_fwd", F, Hh, Ww, C, Tn)) return e;
   if (stj_is16(dtype) && ws_enabled() && outconv_fwd_mfma_try(X, W, bias, Y, F, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride, dtype, stream))
     return stj_check_launch("stj_outconv_fwd(mfma)");
   const size_t lds = (size_t)(18 * 18 * (C + 1) + 9 * C * 2) * 4;
@@ -917,7 +924,7 @@ extern "C" long long stj_outconv_bwd_workspace_bytes() { return outconv_bwd_ws_b
 extern "C" int stj_outconv_bwd(const void* X, const float* W, const float* dY, void* dX, float* dW, float* db, int F, int Hh, int Ww,
                                int C, int Tn, long long y_bstride, long long y_tstride, long long y_pstride, int elu_in, void* ws,
                                long long ws_bytes, int dtype, hipStream_t stream) {
-  if (Hh % OC_T || Ww % OC_T || C % 8) { stj_set_error("outconv: H,W must be multiples of 16 and C of 8"); return STJ_EINVAL; }
+  if (int e = outconv_check("stj_outconv_bwd", F, Hh, Ww, C, Tn)) return e;
   if (dW == nullptr || db == nullptr) { stj_set_error("stj_outconv_bwd: dW / db must not be NULL"); return STJ_EINVAL; }
   if (dtype == STJ_BF16 && ws_enabled() && outconv_bwd_mfma_try(X, W, dY, dX, dW, db, F, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride, elu_in, ws, ws_bytes, stream))
     return stj_check_launch("stj_outconv_bwd(mfma)");

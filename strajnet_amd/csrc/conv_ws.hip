@@ -1449,7 +1449,8 @@ __global__ __launch_bounds__(64) void outconv_bwd_reduce_kernel(const float* __r
 
 bool outconv_fwd_mfma_try(const void* X, const float* W, const float* bias, float* Y, int F, int Hh, int Ww, int C, int Tn,
                           long long y_bs, long long y_ts, long long y_ps, int dtype, hipStream_t st) {
-  if (C != 48 || Hh % OCM_T || Ww % OCM_T || (y_ps & 1) || (((uintptr_t)Y) & 7)) return false;
+  // the kernel moves float2 at Y + b*y_bs + t*y_ts + p*y_ps: every stride even and the base 8-byte aligned, or the generic kernel runs
+  if (C != 48 || Hh % OCM_T || Ww % OCM_T || ((y_bs | y_ts | y_ps) & 1) || (((uintptr_t)Y) & 7)) return false;
   const int ntiles = F * (Hh / OCM_T) * (Ww / OCM_T);
   const int dbg = 0, nbm = 768;
   const int nb = min(ntiles, nbm);
@@ -1460,7 +1461,7 @@ bool outconv_fwd_mfma_try(const void* X, const float* W, const float* bias, floa
 long long outconv_bwd_ws_bytes() { return (long long)OCB_MAXBLK * OCB_PART * sizeof(float); }
 bool outconv_bwd_mfma_try(const void* X, const float* W, const float* dY, void* dX, float* dW, float* db, int F, int Hh, int Ww, int C,
                           int Tn, long long y_bs, long long y_ts, long long y_ps, int elu_in, void* ws, long long ws_bytes, hipStream_t st) {
-  if (C != 48 || Hh % OCM_T || Ww % OCM_T || (y_ps & 1) || (((uintptr_t)dY) & 7)) return false;
+  if (C != 48 || Hh % OCM_T || Ww % OCM_T || ((y_bs | y_ts | y_ps) & 1) || (((uintptr_t)dY) & 7)) return false;
   if (!ws || ws_bytes < outconv_bwd_ws_bytes()) return false;
   const int ntiles = F * (Hh / OCM_T) * (Ww / OCM_T);
   const int nblk = min(ntiles, OCB_MAXBLK);          // 3 resident blocks per CU (168 VGPRs, 39 KB LDS): measured best of 512/768/1024
