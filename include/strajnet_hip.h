@@ -27,6 +27,9 @@ enum stj_status { STJ_OK = 0, STJ_EINVAL = -1, STJ_ELAUNCH = -2, STJ_EUNSUPPORTE
 enum stj_dtype { STJ_F32 = 0, STJ_BF16 = 1, STJ_F16 = 2 };
 enum stj_act { STJ_ACT_NONE = 0, STJ_ACT_GELU = 1, STJ_ACT_ELU = 2 };
 enum stj_unary { STJ_U_GELU = 1, STJ_U_ELU = 2, STJ_U_TANH_SCALE = 3 };
+/* STJ_HEAD_CZ: channels of the inference heads' projected tensor Z (stj_upconv_fwd_head -> stj_outconv_pair_gather): 18 (9 taps x 2
+ * outputs) + 2 zero channels = whole 8-byte pieces (24 until round 6: 17 % more z traffic) */
+enum stj_shape { STJ_HEAD_CZ = 20 };
 
 const char* stj_last_error(void);
 int stj_abi_version(void);

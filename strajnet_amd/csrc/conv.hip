@@ -291,12 +291,21 @@ __global__ __launch_bounds__(256) void upconv_dgrad_kernel(const T* dP, const T*
 // All loads, LDS writes and stores are unconditional (clamped halo addresses, zeroed at the commit through a pinned mask: conv_ws.hip
 // has the story), so the commit's wait counts only what it needs.
 // ---------------------------------------------------------------------------------------------------
+// LDS layout of upconv_dgrad_pf_kernel (16-bit elements): one K chunk of the dP halo [HPIX][LDK], then of the 16 tap matrices [16][BN][LDK]
+template <int FN>
+struct DgradPfGeo {
+  static constexpr int BN = FN * 16, LDK = KC + 8;
+  static constexpr int HH = 2 * TILE_H + 2, HW = 2 * TILE_W + 2, HPIX = HH * HW;
+  static constexpr int LDS_BYTES = (HPIX * LDK + 16 * BN * LDK) * 2;
+  static_assert(LDS_BYTES <= 160 * 1024, "the layout fits the CU's LDS");
+};
 template <typename T, int FN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void upconv_dgrad_pf_kernel(const T* __restrict__ dP, const T* __restrict__ Wd, T* __restrict__ dX,
                                                                  const T* __restrict__ Xelu, int F, int Hi, int Wi, int Cin, int Cout, int ntiles, int nseq) {
   static_assert(sizeof(T) == 2, "16-bit operands");
-  constexpr int BN = FN * 16, LDK = KC + 8, CPR = KC / 8;
-  constexpr int HH = 2 * TILE_H + 2, HW = 2 * TILE_W + 2, HPIX = HH * HW;
+  using G = DgradPfGeo<FN>;
+  constexpr int BN = G::BN, LDK = G::LDK, CPR = KC / 8;
+  constexpr int HW = G::HW, HPIX = G::HPIX;
   constexpr int NH = (HPIX * CPR + 255) / 256, NB = 16 * BN * CPR / 256;
   static_assert(16 * BN * CPR % 256 == 0, "tap matrices split evenly over the threads");
   extern __shared__ __attribute__((aligned(16))) unsigned char pf_smem[];
@@ -446,9 +455,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 template <typename T>
 static bool upconv_dgrad_pf_try(const void* dP, const void* Wd, void* dX, const void* Xelu, int F, int Hi, int Wi, int Cin, int Cout, hipStream_t st) {
   if (stj_no_ws() || Hi % TILE_H || Wi % TILE_W || Cin % 64 || Cout % KC || Cin <= 128) return false;
-  constexpr int FN = 4, BN = FN * 16, LDK = KC + 8;
-  const size_t lds = (size_t)((2 * TILE_H + 2) * (2 * TILE_W + 2) * LDK + 16 * BN * LDK) * sizeof(T);
-  if (!stj_reserve_lds<upconv_dgrad_pf_kernel<T, FN>>((int)lds)) return false;
+  constexpr int FN = 4, BN = FN * 16, lds = DgradPfGeo<FN>::LDS_BYTES;
+  if (!stj_reserve_lds<upconv_dgrad_pf_kernel<T, FN>>(lds)) return false;
   const int ntiles = (Wi / TILE_W) * (Hi / TILE_H) * F, ct = Cin / BN;
   // tile sequences: a multiple of 8 (whole XCD rounds of the work map) with all their workgroups resident at once (one per CU, 32 CUs
   // per XCD -- with 85 sequences x 3 cin tiles five XCDs got 33 workgroups and the kernel took two rounds)
@@ -698,13 +706,24 @@ extern "C" int stj_upconv_wgrad(const void* X, const void* dP, float* dWeff, flo
 // land directly in the [B,H,W,8*4] result (channel 4t + {0,1} / {2,3}).  Y is f32 (model output).
 // ---------------------------------------------------------------------------------------------------
 #define OC_T 16
+// LDS layout of the two generic kernels, in floats; C is a run-time argument, so the struct holds the layout's constants and the size as
+// a function of C: the X halo [HPIX][C + PAD], the weights [9][C][2] and, backward only, the dY halo [HPIX][2].
+// The kernels form their two offsets (HPIX * LDC, then TAPS * C * 2) from these constants themselves, on purpose: with the offsets as
+// functions of the struct (ws_off(C), dys_off(C)) the compiler hoisted the multiplication elsewhere and all six instantiations came out
+// with other instructions (4-5 fewer lines, other registers).  Leave it so unless a change of the generated code is the goal.
+template <bool BWD>
+struct OutconvGeo {
+  static constexpr int HPIX = 18 * 18, PAD = 1, TAPS = 9;
+  static constexpr size_t lds_bytes(int C) { return (size_t)(HPIX * (C + PAD) + TAPS * C * 2 + (BWD ? HPIX * 2 : 0)) * 4; }
+};
 template <typename T>
 __global__ __launch_bounds__(256) void outconv_fwd_kernel(const T* X, const float* W, const float* bias, float* Y, int Hh, int Ww,
                                                           int C, int Tn, long long y_bstride, long long y_tstride, long long y_pstride) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int LDC = C + 1;
+  using G = OutconvGeo<false>;
+  const int LDC = C + G::PAD;
   float* halo = smem;                       // [18*18][C+1]
-  float* Ws = smem + 18 * 18 * LDC;         // [9][C][2]
+  float* Ws = smem + G::HPIX * LDC;         // [9][C][2]
   const int tid = threadIdx.x;
   const int tiles_x = Ww / OC_T, tiles_y = Hh / OC_T;
   int bid = blockIdx.x;
@@ -748,10 +767,11 @@ __global__ __launch_bounds__(256) void outconv_bwd_kernel(const T* X, const floa
                                                           int F, int Hh, int Ww, int C, int Tn, long long y_bstride, long long y_tstride,
                                                           long long y_pstride, int elu_in) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int LDC = C + 1;
+  using G = OutconvGeo<true>;
+  const int LDC = C + G::PAD;
   float* halo = smem;                       // X halo [18*18][C+1]
-  float* Ws = halo + 18 * 18 * LDC;         // [9][C][2]
-  float* dys = Ws + 9 * C * 2;              // dY halo [18*18][2]
+  float* Ws = halo + G::HPIX * LDC;         // [9][C][2]
+  float* dys = Ws + G::TAPS * C * 2;        // dY halo [18*18][2]
   const int tid = threadIdx.x;
   const int tiles_x = Ww / OC_T, tiles_y = Hh / OC_T;
   const int ntiles = F * tiles_x * tiles_y;
@@ -855,7 +875,7 @@ extern "C" int stj_outconv_fwd(const void* X, const float* W, const float* bias,
   if (int e = outconv_check("stj_outconv_fwd", F, Hh, Ww, C, Tn)) return e;
   if (stj_is16(dtype) && ws_enabled() && outconv_fwd_mfma_try(X, W, bias, Y, F, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride, dtype, stream))
     return stj_check_launch("stj_outconv_fwd(mfma)");
-  const size_t lds = (size_t)(18 * 18 * (C + 1) + 9 * C * 2) * 4;
+  const size_t lds = OutconvGeo<false>::lds_bytes(C);
   if (lds > 160 * 1024) { stj_set_error("outconv: C=%d too large for LDS", C); return STJ_EUNSUPPORTED; }
   const int grid = F * (Hh / OC_T) * (Ww / OC_T);
   bool reserved = false;      // lds depends on C: the reservation grows with it
@@ -928,7 +948,7 @@ extern "C" int stj_outconv_bwd(const void* X, const float* W, const float* dY, v
   if (dW == nullptr || db == nullptr) { stj_set_error("stj_outconv_bwd: dW / db must not be NULL"); return STJ_EINVAL; }
   if (dtype == STJ_BF16 && ws_enabled() && outconv_bwd_mfma_try(X, W, dY, dX, dW, db, F, Hh, Ww, C, Tn, y_bstride, y_tstride, y_pstride, elu_in, ws, ws_bytes, stream))
     return stj_check_launch("stj_outconv_bwd(mfma)");
-  const size_t lds = (size_t)(18 * 18 * (C + 1) + 9 * C * 2 + 18 * 18 * 2) * 4;
+  const size_t lds = OutconvGeo<true>::lds_bytes(C);
   if (lds > 160 * 1024 || 9 * C > 1024) { stj_set_error("outconv: C=%d too large", C); return STJ_EUNSUPPORTED; }
   const int grid = min(1024, F * (Hh / OC_T) * (Ww / OC_T));
   bool reserved = false;      // as in stj_outconv_fwd

@@ -23,15 +23,28 @@
 // TH = rows of the low-res tile.  16 (round 6): the workgroup's weight stream -- every workgroup reads all 16 tap matrices of its cout block,
 // 393 KB at Cin = 384, and with 8-row tiles that was 302 of the 400 MB the 384 -> 192 launch pulls out of L2, the level this kernel saturates
 // (~6 TB/s) -- is amortised over twice the pixels; the epilogue goes through the LDS stage in two halves so that two workgroups still share a CU.
+// LDS layout of upconv_fwd_ps_kernel (16-bit elements): two halo chunk buffers [HPIX][LDK]; the output stage of the epilogue (half a
+// 16-row tile: 16 output rows x 32 pixels, stride LDO) aliases them.
+template <int FN, int TH>
+struct PsGeo {
+  static constexpr int LDK = PS_KC + 16;               // 96-byte pixel stride: 2 (mod 4) 16-byte slots, conflict-free b128 fragment reads
+  static constexpr int CT = FN * 16, LDO = CT + 8;
+  static constexpr int HPIX = (TH + 2) * PS_HW;        // 180 / 324
+  static constexpr int HALO_BYTES = 2 * HPIX * LDK * 2, STAGE_BYTES = 2 * 8 * 2 * PS_TW * LDO * 2;
+  static constexpr int LDS_BYTES = HALO_BYTES > STAGE_BYTES ? HALO_BYTES : STAGE_BYTES;
+  static_assert(LDS_BYTES <= 160 * 1024, "the layout fits the CU's LDS");
+};
 template <typename T, int FN, int MINB, int TH>
 __global__ __launch_bounds__(256, MINB) void upconv_fwd_ps_kernel(const T* __restrict__ X, const T* __restrict__ Wf,
                                                                   const float* __restrict__ bias, T* __restrict__ Y,
                                                                   const T* __restrict__ R1, T* __restrict__ Y2, const T* __restrict__ R2,
                                                                   int F, int Hi, int Wi, int Cin, int Cout) {
-  constexpr int LDK = PS_KC + 16;                  // 96-byte pixel stride: 2 (mod 4) 16-byte slots, conflict-free b128 fragment reads
-  constexpr int CT = FN * 16, LDO = CT + 8;
-  constexpr int PS_TH = TH, PS_HH = TH + 2;
-  constexpr int HPIX = PS_HH * PS_HW;              // 180 / 324
+  static_assert(sizeof(T) == 2, "16-bit operands");
+  using G = PsGeo<FN, TH>;
+  constexpr int LDK = G::LDK;
+  constexpr int CT = G::CT, LDO = G::LDO;
+  constexpr int PS_TH = TH;
+  constexpr int HPIX = G::HPIX;
   constexpr int NCH = (HPIX * 4 + 255) / 256;      // 16-byte chunks per thread per halo chunk (3)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   T* halo0 = reinterpret_cast<T*>(smem_raw);
@@ -205,10 +218,8 @@ __global__ __launch_bounds__(256, MINB) void upconv_fwd_ps_kernel(const T* __res
 
 template <typename T, int FN, int MINB, int TH>
 static bool fwd_ps_launch(const void* X, const void* Wf, const float* bias, void* Y, const void* R1, void* Y2, const void* R2, int F, int Hi, int Wi, int Cin, int Cout, hipStream_t st) {
-  constexpr int LDK = PS_KC + 16, CT = FN * 16, LDO = CT + 8;
-  const size_t lds_h = (size_t)2 * (TH + 2) * PS_HW * LDK * 2, lds_o = (size_t)2 * 8 * 2 * PS_TW * LDO * 2;
-  const size_t lds = lds_h > lds_o ? lds_h : lds_o;
-  if (!stj_reserve_lds<upconv_fwd_ps_kernel<T, FN, MINB, TH>>((int)lds)) return false;
+  constexpr int CT = FN * 16, lds = PsGeo<FN, TH>::LDS_BYTES;
+  if (!stj_reserve_lds<upconv_fwd_ps_kernel<T, FN, MINB, TH>>(lds)) return false;
   const int tiles = ((Wi + PS_TW - 1) / PS_TW) * ((Hi + TH - 1) / TH) * F;
   hipLaunchKernelGGL((upconv_fwd_ps_kernel<T, FN, MINB, TH>), dim3(tiles, (Cout + CT - 1) / CT), dim3(256), lds, st, (const T*)X, (const T*)Wf, bias,
                      (T*)Y, (const T*)R1, (T*)Y2, (const T*)R2, F, Hi, Wi, Cin, Cout);

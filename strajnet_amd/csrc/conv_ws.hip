@@ -11,6 +11,10 @@
 //   * the input halo (10 x 18 low-res pixels x Cin) is double buffered: the next tile's global loads are issued before
 //     the MFMA loop and written to the other LDS buffer after it;
 //   * results (bias + ELU applied) are staged in LDS and leave as full rows of 8-byte segments, coalesced.
+// The file has grown beyond that kernel.  It holds, each under its own banner: the wave-specialised forward (with the inference heads'
+// epilogue), the transpose-read weight gradient (tr, tr4), the MFMA output heads (forward, pair, gather, backward, reduce) and the
+// weight-stationary input gradients (ws, ws2).  The entry points that try them are in conv.hip.  Every kernel here with dynamic LDS
+// takes its layout from a ...Geo struct in front of it, and its launcher takes the byte count from the same struct.
 #include "common.h"
 #include "quantize.h"
 #include <stdlib.h>
@@ -25,7 +29,6 @@
 #ifndef WS2_PF
 #define WS2_PF 6        // ... upconv_fwd_ws2_kernel (2 / 4 / 6: 209 / 199 / 194 us; 7 spills)
 #endif
-#define HEAD_CZ 20         // channels of the inference heads' projected tensor z: 18 (9 taps x 2 outputs) + 2 zero channels = whole 8-byte pieces (24 until round 6: 17 % more z traffic)
 #define WS_TH 8
 #define WS_TW 16
 #define WS_HW (WS_TW + 2)
@@ -51,26 +54,42 @@
 // projection z[q][tap, o] = sum_c Wh[tap][c][o] y[q][c]: 18 numbers per pixel instead of 48, and no halo -- y never leaves the chip.  The
 // ELU outputs a lane holds after the main MFMAs (D layout: channels 16 n + 4 g + r of ITS pixel) ARE an MFMA B operand for pixel = column
 // if the head weights (A operand, rows = (tap, o)) are laid out with the same k order -- the contraction order is free -- so z costs 4 more
-// MFMAs per 16 pixels and no data movement.  Y is then the z tensor [F, 2 Hi, 2 Wi, HEAD_CZ = 20] (18 + 2 zero channels: whole 8-byte pieces), which
+// MFMAs per 16 pixels and no data movement.  Y is then the z tensor [F, 2 Hi, 2 Wi, STJ_HEAD_CZ = 20] (18 + 2 zero channels: whole 8-byte pieces), which
 // stj_outconv_pair_gather sums over the 9 neighbours: 48 + 48 bytes per pixel of traffic instead of 96 + 96.
+// LDS layout of upconv_fwd_ws2_kernel (16-bit elements): two halo buffers [HPIX][LDK], then two output-stage buffers.
+template <int KS, int NF, bool HEAD>
+struct Ws2Geo {
+  static constexpr int CIN = KS * 32, CT = NF * 16;
+  static constexpr int LDK = CIN + 16;                   // halo pixel stride
+  static constexpr int LDO = HEAD ? 40 : CT + 8;         // stage pixel stride
+  static constexpr int HPIX = WS_HH * WS_HW;
+  static constexpr int SR = 4;                           // low-res rows per step
+  static constexpr int OST = 2 * SR * (2 * WS_TW) * LDO; // one output-stage buffer: 2*SR output rows x 32 pixels
+  static constexpr int OST_ALLOC = 2 * SR * (2 * WS_TW) * (CT + 8);   // (the z stage of HEAD is smaller than the y stage it replaces and keeps its allocation)
+  static constexpr int HALO_BYTES = 2 * HPIX * LDK * 2;  // both halo buffers; the stage buffers follow (the kernel's ost0)
+  static constexpr int LDS_BYTES = HALO_BYTES + 2 * OST_ALLOC * 2;
+  static_assert(OST <= OST_ALLOC && LDS_BYTES <= 160 * 1024, "the layout fits its allocation and the CU's LDS");
+};
 template <typename T, int KS, int NF, bool EXACT, bool HEAD = false, int XCT = 0>
 __global__ __launch_bounds__(512, 1) void upconv_fwd_ws2_kernel(const T* __restrict__ X, const T* __restrict__ Wf,
                                                              const float* __restrict__ bias, T* __restrict__ Y,
                                                              int F, int Hi, int Wi, int Cout_, int ntiles, int dbg, const float* __restrict__ Wh) {
-  constexpr int CIN = KS * 32;
+  static_assert(sizeof(T) == 2, "16-bit operands");
+  using G = Ws2Geo<KS, NF, HEAD>;
+  constexpr int CIN = G::CIN;
   constexpr bool XMAP = XCT > 1;
-  constexpr int LDK = CIN + 16;
-  constexpr int CT = NF * 16;
-  constexpr int CTO = HEAD ? HEAD_CZ : CT;               // channels of a stage pixel / of the result
-  constexpr int LDO = HEAD ? 40 : CT + 8;
+  constexpr int LDK = G::LDK;
+  constexpr int CT = G::CT;
+  constexpr int CTO = HEAD ? STJ_HEAD_CZ : CT;           // channels of a stage pixel / of the result
+  constexpr int LDO = G::LDO;
   const int Cout = HEAD ? CT : Cout_;                    // channels of the convolution itself
-  const int Cres = HEAD ? HEAD_CZ : Cout_;               // channels of the tensor the movers write
+  const int Cres = HEAD ? STJ_HEAD_CZ : Cout_;           // channels of the tensor the movers write
   static_assert(!HEAD || (NF == 3 && EXACT), "the head epilogue is written for the 48-channel level, whole tiles");
-  constexpr int HPIX = WS_HH * WS_HW;
+  constexpr int HPIX = G::HPIX;
   constexpr int CPP = CIN / 8;
   constexpr int NCH = (HPIX * CPP + 255) / 256;          // halo chunks per mover thread
-  constexpr int SR = 4;                                  // low-res rows per step
-  constexpr int OST = 2 * SR * (2 * WS_TW) * LDO;        // one output-stage buffer: 2*SR output rows x 32 pixels
+  constexpr int SR = G::SR;
+  constexpr int OST = G::OST;
   constexpr int STEPS = WS_TH / SR;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   T* halo0 = reinterpret_cast<T*>(smem_raw);
@@ -196,7 +215,7 @@ __global__ __launch_bounds__(512, 1) void upconv_fwd_ws2_kernel(const T* __restr
               f32x4 z = (f32x4){0.f, 0.f, 0.f, 0.f};
               z = Mma<T>::mma(hwr[tf][0], y0, z);
               z = Mma<T>::mma(hwr[tf][1], y1, z);
-              if (tf == 0 || 16 + 4 * g < HEAD_CZ) *reinterpret_cast<uint2*>(zp + 16 * tf + 4 * g) = make_uint2(pack2<T>(z[0], z[1]), pack2<T>(z[2], z[3]));
+              if (tf == 0 || 16 + 4 * g < STJ_HEAD_CZ) *reinterpret_cast<uint2*>(zp + 16 * tf + 4 * g) = make_uint2(pack2<T>(z[0], z[1]), pack2<T>(z[2], z[3]));
             }
           } else {
 #pragma unroll
@@ -381,9 +400,8 @@ __global__ __launch_bounds__(512, 1) void upconv_fwd_ws2_kernel(const T* __restr
 
 template <typename T, int KS, int NF, bool EXACT>
 static bool ws2_launch_t(const void* X, const void* Wf, const float* bias, void* Y, int F, int Hi, int Wi, int Cout, hipStream_t st) {
-  constexpr int CIN = KS * 32, LDK = CIN + 16, CT = NF * 16, LDO = CT + 8;
-  const size_t lds = (size_t)(2 * WS_HH * WS_HW * LDK + 2 * 8 * 2 * WS_TW * LDO) * 2;
-  if (!stj_reserve_lds<upconv_fwd_ws2_kernel<T, KS, NF, EXACT>>((int)lds)) return false;
+  constexpr int CT = NF * 16, lds = Ws2Geo<KS, NF, false>::LDS_BYTES;
+  if (!stj_reserve_lds<upconv_fwd_ws2_kernel<T, KS, NF, EXACT>>(lds)) return false;
   const int ntiles = ((Wi + WS_TW - 1) / WS_TW) * ((Hi + WS_TH - 1) / WS_TH) * F;
   const int ct = (Cout + CT - 1) / CT;
   int nblk = 256 / ct;
@@ -398,7 +416,7 @@ static bool ws2_launch_t(const void* X, const void* Wf, const float* bias, void*
     // (ntiles no multiple of 8 and below 80) would store one step of stage beyond Y.  Such a shape takes the 2-D grid, whose walkers
     // all have a tile; the guarded movers test every tile.
     if (ct == 3 && ntiles >= 8 && (!EXACT || nw <= ntiles)) {
-      if (!stj_reserve_lds<upconv_fwd_ws2_kernel<T, KS, NF, EXACT, false, 3>>((int)lds)) return false;
+      if (!stj_reserve_lds<upconv_fwd_ws2_kernel<T, KS, NF, EXACT, false, 3>>(lds)) return false;
       hipLaunchKernelGGL((upconv_fwd_ws2_kernel<T, KS, NF, EXACT, false, 3>), dim3(nw * 3), dim3(512), lds, st, (const T*)X, (const T*)Wf, bias, (T*)Y, F, Hi, Wi, Cout,
                          ntiles, dbg, (const float*)nullptr);
       return true;
@@ -408,12 +426,11 @@ static bool ws2_launch_t(const void* X, const void* Wf, const float* bias, void*
                      (const float*)nullptr);
   return true;
 }
-// the 96 -> 48 level with the 48 -> 2 head's channel projection in its epilogue: Z [F, 2 Hi, 2 Wi, HEAD_CZ] instead of Y (whole tiles only)
+// the 96 -> 48 level with the 48 -> 2 head's channel projection in its epilogue: Z [F, 2 Hi, 2 Wi, STJ_HEAD_CZ] instead of Y (whole tiles only)
 template <typename T>
 static bool ws2_head_launch(const void* X, const void* Wf, const float* bias, const float* Wh, void* Z, int F, int Hi, int Wi, hipStream_t st) {
-  constexpr int KS = 3, NF = 3, CIN = KS * 32, LDK = CIN + 16, CT = NF * 16, LDO = CT + 8;
-  const size_t lds = (size_t)(2 * WS_HH * WS_HW * LDK + 2 * 8 * 2 * WS_TW * LDO) * 2;       // (the z stage is smaller than the y stage it replaces)
-  if (!stj_reserve_lds<upconv_fwd_ws2_kernel<T, KS, NF, true, true>>((int)lds)) return false;
+  constexpr int KS = 3, NF = 3, CT = NF * 16, lds = Ws2Geo<KS, NF, true>::LDS_BYTES;
+  if (!stj_reserve_lds<upconv_fwd_ws2_kernel<T, KS, NF, true, true>>(lds)) return false;
   const int ntiles = (Wi / WS_TW) * (Hi / WS_TH) * F;
   const int nblk = ntiles < 256 ? ntiles : 256;
   hipLaunchKernelGGL((upconv_fwd_ws2_kernel<T, KS, NF, true, true>), dim3(nblk, 1), dim3(512), lds, st, (const T*)X, (const T*)Wf, bias, (T*)Z, F, Hi, Wi, CT, ntiles, 0, Wh);
@@ -627,21 +644,33 @@ __global__ __launch_bounds__(256, 2) void upconv_wgrad_tr_kernel(const bf16* __r
 // pair of the 96 -> 48 layer); every wave reads its own column parity / tap through its transpose-read addresses.  (All four phases in
 // one 1024-thread workgroup would stage 82 KB, but at 128 VGPRs per lane the 72 accumulator registers leave no room for the
 // register-staged prefetch: 140-196 bytes of scratch per lane.)
+// LDS layout of upconv_wgrad_tr4_kernel (bf16): TWO stages of BUF elements, each the dP image [CR][2 CW][LDO] and then the X image
+// [CR + 1][CW + 2][LDI]; the strides are explained where the kernel takes them
+template <int FO, int FI, int CW, int NPIX>
+struct WgradTr4Geo {
+  static constexpr int CR = NPIX / CW, BO = FO * 16, BI = FI * 16;
+  static constexpr int LDO = BO + 8, LDI = (BI / 16) % 2 ? BI : BI + 16;
+  static constexpr int YW = 2 * CW, YR = CR, XW = CW + 2, XR = CR + 1;
+  static constexpr int BUF = YR * YW * LDO + XR * XW * LDI;
+  static constexpr int LDS_BYTES = 2 * BUF * 2;
+  static_assert(LDS_BYTES <= 160 * 1024, "the layout fits the CU's LDS");
+};
 template <int FO, int FI, int CW, int NPIX>
 __global__ __launch_bounds__(512, 2) void upconv_wgrad_tr4_kernel(const bf16* __restrict__ X, const bf16* __restrict__ dP,
                                                                   float* dWeff, float* dbias, int db_parts, int F, int Hi, int Wi, int Cin,
                                                                   int Cout, int chunks_per_block, int nstrips, int ntiles) {
-  constexpr int CR = NPIX / CW, KROWS = 32 / CW;          // NPIX low-res pixels per barrier pair (NPIX / 32 k-steps)
-  constexpr int BO = FO * 16, BI = FI * 16;
+  using G = WgradTr4Geo<FO, FI, CW, NPIX>;
+  constexpr int CR = G::CR, KROWS = 32 / CW;              // NPIX low-res pixels per barrier pair (NPIX / 32 k-steps)
+  constexpr int BO = G::BO, BI = G::BI;
   // row strides: consecutive low-res pixels lie 2 hi-res columns = LDO dwords apart in the dP image and LDI / 2 dwords apart in the X
   // image; both 8 * odd dwords, so the 8 consecutive pixels of a 32-lane transpose-read pass (k-permutation below) hit disjoint banks
-  constexpr int LDO = BO + 8, LDI = (BI / 16) % 2 ? BI : BI + 16;
+  constexpr int LDO = G::LDO, LDI = G::LDI;
   static_assert((LDO / 8) % 2 == 1 && (LDI / 16) % 2 == 1 && LDI % 16 == 0, "conflict-free transpose-read strides");
-  constexpr int YW = 2 * CW, YR = CR, XW = CW + 2, XR = CR + 1;
+  constexpr int YW = G::YW, YR = G::YR, XW = G::XW, XR = G::XR;
   constexpr int DY_CH = YR * YW * (BO / 8), X_CH = XR * XW * (BI / 8);
   constexpr int NCH = (DY_CH + X_CH + 511) / 512;
   extern __shared__ __attribute__((aligned(16))) unsigned char w4_smem[];
-  constexpr int BUF = YR * YW * LDO + XR * XW * LDI;       // elements of one stage; TWO stages: the next chunk is written while this one
+  constexpr int BUF = G::BUF;                              // elements of one stage; TWO stages: the next chunk is written while this one
   bf16* dYs = reinterpret_cast<bf16*>(w4_smem);            // is read -- one barrier per chunk.  [CR][2 CW][LDO]: hi-res dP rows 2 (i0 + ri) + a
   bf16* Xs = dYs + YR * YW * LDO;                          // [CR + 1][CW + 2][LDI]: X rows i0 + a - 1 .., columns j0 - 1 ..
 
@@ -782,9 +811,8 @@ __global__ __launch_bounds__(512, 2) void upconv_wgrad_tr4_kernel(const bf16* __
 template <int FO, int FI, int CW, int NPIX>
 static bool wgrad_tr4_launch(const void* X, const void* dP, float* dWeff, float* dbias, int db_parts, int F, int Hi, int Wi, int Cin, int Cout,
                              int tiles, int wg_budget, hipStream_t st) {
-  constexpr int CR = NPIX / CW, BO = FO * 16, BI = FI * 16;
-  const size_t lds = (size_t)2 * (CR * 2 * CW * (BO + 8) + (CR + 1) * (CW + 2) * ((BI / 16) % 2 ? BI : BI + 16)) * 2;
-  if (!stj_reserve_lds<upconv_wgrad_tr4_kernel<FO, FI, CW, NPIX>>((int)lds)) return false;
+  constexpr int CR = NPIX / CW, lds = WgradTr4Geo<FO, FI, CW, NPIX>::LDS_BYTES;
+  if (!stj_reserve_lds<upconv_wgrad_tr4_kernel<FO, FI, CW, NPIX>>(lds)) return false;
   const long long nchunks = (long long)F * (Hi / CR) * (Wi / CW);
   // Workgroups: HALF the CUs.  Alone the kernel is faster with one workgroup per CU (246 vs 344 us for the 96 -> 48 layer), but the
   // decoder's weight gradients are deferred (ops.py) and run next to the backward of the cross-attentions / FG-MSA / the encoder, chains
@@ -1117,7 +1145,7 @@ bool outconv_pair_fwd_try(const void* X0, const void* X1, const float* W0, const
 
 // Second half of the inference heads (first half: the HEAD epilogue of upconv_fwd_ws2_kernel): Y[b, y, x, 4 t + 2 h + o] = bias_h[o] +
 // sum over the 9 neighbours (ky, kx) of Z_h[f(b, t), y + ky - 1, x + kx - 1, 2 (3 ky + kx) + o] (zero outside the image), Z_h the projected
-// tensors [F, H, W, HEAD_CZ = 20] of the two decoder branches.  A workgroup owns a 16 x 16 spatial tile of one scene and walks its 16 (waypoint,
+// tensors [F, H, W, STJ_HEAD_CZ = 20] of the two decoder branches.  A workgroup owns a 16 x 16 spatial tile of one scene and walks its 16 (waypoint,
 // head) planes through an 18 x 18 halo in LDS (next plane prefetched in registers); a thread keeps the 32 results of its pixel and writes
 // one full 128-byte line.
 // QUANT (stj_outconv_pair_gather_q): the same sums, but the epilogue turns the 32 results into the challenge format's bytes (quantize.h)
@@ -1127,7 +1155,7 @@ template <typename T, bool QUANT>
 __global__ __launch_bounds__(256) void outconv_pair_gather_kernel(const T* __restrict__ Z0, const T* __restrict__ Z1, const float* __restrict__ b0,
                                                                   const float* __restrict__ b1, std::conditional_t<QUANT, uint8_t, float>* __restrict__ Y,
                                                                   int B, int Hh, int Ww, int t_major, int nsp) {
-  constexpr int CZ = HEAD_CZ, LDZ = HEAD_CZ, CPP = CZ / 4, NPX = OCM_H * OCM_H, NCHK = NPX * CPP, NCH = (NCHK + 255) / 256;      // 8-byte pieces
+  constexpr int CZ = STJ_HEAD_CZ, LDZ = STJ_HEAD_CZ, CPP = CZ / 4, NPX = OCM_H * OCM_H, NCHK = NPX * CPP, NCH = (NCHK + 255) / 256;      // 8-byte pieces
   __shared__ __attribute__((aligned(16))) T halo[NPX * LDZ];
   const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
   const int tiles_x = Ww / OCM_T, tiles_y = Hh / OCM_T;
@@ -1478,6 +1506,18 @@ bool outconv_bwd_mfma_try(const void* X, const float* W, const float* dY, void* 
 // and leave as coalesced 8-byte segments.  v1 (conv.hip) re-staged 16 tap matrices through LDS per tile: 0.59 ms for
 // 96<-48 @128x128 (profiles/r01_b_*).
 // =====================================================================================================
+// LDS layout of upconv_dgrad_ws_kernel (bf16): the dP halo [HPIX][LDK] (+64 elements of tail), then two partial stages
+// [4 phases][2 rows][16 px][LDR]; the strides are explained where the kernel takes them
+template <int KS, int NFI>
+struct DgradWsGeo {
+  static constexpr int LDK = KS * 32 + 8;
+  static constexpr int HH = 2 * WS_TH + 2, HW = 2 * WS_TW + 2, HPIX = HH * HW;
+  static constexpr int CT = NFI * 16, LDR = CT + 4;
+  static constexpr int RED = 4 * 2 * 16 * LDR;
+  static constexpr int HALO_BYTES = (HPIX * LDK + 64) * 2;
+  static constexpr int LDS_BYTES = HALO_BYTES + 2 * RED * 2;
+  static_assert(LDS_BYTES <= 160 * 1024, "the layout fits the CU's LDS");
+};
 template <int KS, int NFI, bool ELU, int COUT>
 __global__ __launch_bounds__(512, 1) void upconv_dgrad_ws_kernel(const bf16* __restrict__ dP, const bf16* __restrict__ Wd,
                                                                  bf16* __restrict__ dX, const bf16* __restrict__ Xelu, int F, int Hi,
@@ -1487,14 +1527,15 @@ __global__ __launch_bounds__(512, 1) void upconv_dgrad_ws_kernel(const bf16* __r
   // halo pixel stride.  A fragment read takes every OTHER halo pixel (low-res pixel ln <-> high-res 2 ln + v), so consecutive lanes are
   // 2 * LDK apart: conflict-free b128 reads need 2 * LDK = 2 (mod 4) 16-byte slots, i.e. an ODD number of slots per pixel -> +8 elements
   // (9 / 13 slots).  Channels >= Cout stay zero.
-  constexpr int LDK = KS * 32 + 8;
-  constexpr int HH = 2 * WS_TH + 2, HW = 2 * WS_TW + 2, HPIX = HH * HW;
-  constexpr int CT = NFI * 16;                     // cin tile of this workgroup
-  constexpr int LDR = CT + 4;                      // partial-tile row stride (bf16): 34 dwords (two stages + the halo = 158.4 KB of the 160)
-  constexpr int RED = 4 * 2 * 16 * LDR;            // one partial stage: [4 phases][2 rows][16 px][LDR]
+  using G = DgradWsGeo<KS, NFI>;
+  constexpr int LDK = G::LDK;
+  constexpr int HH = G::HH, HW = G::HW, HPIX = G::HPIX;
+  constexpr int CT = G::CT;                        // cin tile of this workgroup
+  constexpr int LDR = G::LDR;                      // partial-tile row stride (bf16): 34 dwords (two stages + the halo = 158.4 KB of the 160)
+  constexpr int RED = G::RED;                      // one partial stage: [4 phases][2 rows][16 px][LDR]
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   bf16* halo = reinterpret_cast<bf16*>(smem_raw);                         // [HPIX][LDK] (+64 tail)
-  bf16* red0 = reinterpret_cast<bf16*>(smem_raw + (size_t)(HPIX * LDK + 64) * 2);   // 2 stages
+  bf16* red0 = reinterpret_cast<bf16*>(smem_raw + G::HALO_BYTES);         // 2 stages
   constexpr int CPP = Cout / 8;                    // 16-byte chunks per halo pixel (Cout <= KS*32)
   static_assert(COUT % 8 == 0 && COUT <= KS * 32, "halo pixel holds KS*32 channels");
   // 8 waves: wave = (input phase (a,b), half of the cin tile), 96 weight VGPRs each, two waves per SIMD.  A pass (2 low-res rows) is ONE
@@ -1679,9 +1720,8 @@ __global__ __launch_bounds__(512, 1) void upconv_dgrad_ws_kernel(const bf16* __r
 
 template <int KS, int NFI, bool ELU, int COUT>
 static bool dgrad_ws_launch2(const void* dP, const void* Wd, void* dX, const void* Xelu, int F, int Hi, int Wi, int Cin, int Cout, hipStream_t st) {
-  constexpr int LDK = KS * 32 + 8, HPIX = (2 * WS_TH + 2) * (2 * WS_TW + 2), CT = NFI * 16, LDR = CT + 4;
-  const size_t lds = (size_t)(HPIX * LDK + 64) * 2 + (size_t)2 * 4 * 2 * 16 * LDR * 2;
-  if (!stj_reserve_lds<upconv_dgrad_ws_kernel<KS, NFI, ELU, COUT>>((int)lds)) return false;
+  constexpr int CT = NFI * 16, lds = DgradWsGeo<KS, NFI>::LDS_BYTES;
+  if (!stj_reserve_lds<upconv_dgrad_ws_kernel<KS, NFI, ELU, COUT>>(lds)) return false;
   if ((long long)F * 4 * Hi * Wi * Cout * 2 >= (1LL << 31)) return false;      // the halo loader addresses dP through 32-bit (int) byte offsets
   const int ntiles = ((Wi + WS_TW - 1) / WS_TW) * ((Hi + WS_TH - 1) / WS_TH) * F;
   const int ct = (Cin + CT - 1) / CT;
@@ -1705,15 +1745,27 @@ static bool dgrad_ws_launch2(const void* dP, const void* Wd, void* dX, const voi
 // One workgroup barrier per step (2 low-res rows).
 // =====================================================================================================
 typedef __attribute__((ext_vector_type(4))) short ws_bf16x4;
+// LDS layout of upconv_dgrad_ws2_kernel (bf16, 96 <- 48): the dP halo [HPIX][LDK], then two stage buffers [4 phases][2 rows][16 px][LDR]
+struct DgradWs2Geo {
+  static constexpr int Cout = 48, Cin = 96;
+  static constexpr int LDK = Cout + 8;             // halo pixel: 48 channels + 8 pad = 7 16-byte slots (odd: conflict-free stride-2 reads)
+  static constexpr int HH = 2 * WS_TH + 2, HW = 2 * WS_TW + 2, HPIX = HH * HW;
+  static constexpr int LDR = Cin + 8;              // partial-tile pixel stride (bf16)
+  static constexpr int RED = 4 * 2 * 16 * LDR;
+  static constexpr int HALO_BYTES = HPIX * LDK * 2;      // the stage buffers follow (the kernel's red0)
+  static constexpr int LDS_BYTES = HALO_BYTES + 2 * RED * 2;
+  static_assert(LDS_BYTES <= 160 * 1024, "the layout fits the CU's LDS");
+};
 template <bool ELU, bool V3>
 __global__ __launch_bounds__(512, 1) void upconv_dgrad_ws2_kernel(const bf16* __restrict__ dP, const bf16* __restrict__ Wd,
                                                                   bf16* __restrict__ dX, const bf16* __restrict__ Xelu, int F, int Hi,
                                                                   int Wi, int ntiles, int dbg) {
-  constexpr int Cout = 48, Cin = 96, NFI = 6;
-  constexpr int LDK = 48 + 8;                      // halo pixel: 48 channels + 8 pad = 7 16-byte slots (odd: conflict-free stride-2 reads)
-  constexpr int HH = 2 * WS_TH + 2, HW = 2 * WS_TW + 2, HPIX = HH * HW;
-  constexpr int LDR = Cin + 8;                     // partial-tile pixel stride (bf16)
-  constexpr int RED = 4 * 2 * 16 * LDR;            // one stage buffer: [4 phases][2 rows][16 px][LDR]
+  using G = DgradWs2Geo;
+  constexpr int Cout = G::Cout, Cin = G::Cin, NFI = 6;
+  constexpr int LDK = G::LDK;
+  constexpr int HH = G::HH, HW = G::HW, HPIX = G::HPIX;
+  constexpr int LDR = G::LDR;
+  constexpr int RED = G::RED;                      // one stage buffer: [4 phases][2 rows][16 px][LDR]
   constexpr int CPP = Cout / 8;                    // 16-byte chunks per halo pixel
   constexpr int STEPS = WS_TH / 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -2084,9 +2136,8 @@ __global__ __launch_bounds__(512, 1) void upconv_dgrad_ws2_kernel(const bf16* __
 
 template <bool ELU, bool V3>
 static bool dgrad_ws2_launch(const void* dP, const void* Wd, void* dX, const void* Xelu, int F, int Hi, int Wi, hipStream_t st) {
-  constexpr int LDK = 56, HPIX = (2 * WS_TH + 2) * (2 * WS_TW + 2), LDR = 104;
-  const size_t lds = (size_t)(HPIX * LDK + 2 * 4 * 2 * 16 * LDR) * 2;
-  if (!stj_reserve_lds<upconv_dgrad_ws2_kernel<ELU, V3>>((int)lds)) return false;
+  constexpr int lds = DgradWs2Geo::LDS_BYTES;
+  if (!stj_reserve_lds<upconv_dgrad_ws2_kernel<ELU, V3>>(lds)) return false;
   const int ntiles = ((Wi + WS_TW - 1) / WS_TW) * ((Hi + WS_TH - 1) / WS_TH) * F;
   const int nblk = ntiles < 256 ? ntiles : 256;
   const int dbg = 0;      // (role-ablation mask of the kernel; profiling builds only)

@@ -2434,7 +2434,7 @@ def upconv_head_ok(Hi, Wi, pw, dtype, Tn):
             and Tn == 8 and WS_KERNELS)
 
 
-HEAD_CZ = 20       # channels of the projected tensor z: 9 taps x 2 outputs + 2 zero channels (csrc/conv_ws.hip HEAD_CZ)
+HEAD_CZ = _ENUMS['stj_shape']['STJ_HEAD_CZ']       # channels of the projected tensor z: 9 taps x 2 outputs + 2 zero channels
 
 
 def upconv_head(x, pw, pb, phead, prep=None):

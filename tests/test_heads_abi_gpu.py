@@ -23,7 +23,8 @@ Found by the run: nothing else.  All 117 exact twins (rows x element types x hea
 the single-head MFMA forward, which nothing ran before, nt = 4, the rectangular and t-major rows, the persistent rows (832 tiles on 768
 workgroups forward and backward, 513 spatial tiles on 257 paired workgroups, 273 tiles on 256 in the head epilogue, 2050 on 2048 in the
 gather, 1088 on 1024 in the generic backward) included; Q equals stj_quantize_waypoints of the gather's own Y on every row, and NaN pattern
-in channels 18, 19 of Z changes no bit of Y or Q.  Every refusal holds against the fixed launchers.
+in channels 18, 19 of Z changes no bit of Y or Q.  Every refusal holds against the fixed launchers.  profiles/test_heads_kernels.txt
+lists the kernels one run of this module launched.
 
 Largest |err| / sum |terms| of the random twin per path and element type on an MI355X (MEASURED in _heads_cases.py; the gate is four times
 that where below the bound -- EPS_ELEM[T] = 2^-7 / 2^-10 / 2^-17, 2^-17 for the f32 outputs --, profiles/test_heads_ratios.txt has the
