@@ -16,3 +16,5 @@ from .submission import (QuantizedWaypoints, ResultDrain, quantize_waypoints, qu
                          DEFLATE_SEGMENT, FramedWaypoints, SubmissionWriter, SUBMISSION_SCHEMA, frame_reference,
                          submission_reference, parse_submission)
 from .data import (ResidentPool, ResidentFeed, PoolLayout, PoolWriter, PoolSampler, ShuffleWindow, WindowFeed)     # noqa: F401
+from .raster import (RasterConfig, Tracks, Rasterizer, rasterize, raster_reference, raster_example,     # noqa: F401
+                     tracks_from_motion_example)

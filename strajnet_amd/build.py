@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OUT = os.path.join(HERE, 'libstrajnet_hip.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'strajnet_hip.h')      # the C ABI; csrc/common.h includes it
-SOURCES = ['util.hip', 'gemm.hip', 'wgrad_sk.hip', 'norm.hip', 'patch_embed.hip', 'swin_attn.hip', 'swin_fused.hip', 'xattn_fused.hip', 'fgattn.hip', 'agent_fused.hip', 'fgoff_fused.hip', 'attn.hip', 'conv.hip', 'conv_ws.hip', 'conv_ps.hip', 'loss.hip', 'eval.hip', 'quantize.hip', 'deflate.hip', 'unpack.hip', 'pool.hip', 'pack.hip', 'window.hip', 'rng.hip', 'optim.hip', 'tensorstats.hip']
+SOURCES = ['util.hip', 'gemm.hip', 'wgrad_sk.hip', 'norm.hip', 'patch_embed.hip', 'swin_attn.hip', 'swin_fused.hip', 'xattn_fused.hip', 'fgattn.hip', 'agent_fused.hip', 'fgoff_fused.hip', 'attn.hip', 'conv.hip', 'conv_ws.hip', 'conv_ps.hip', 'loss.hip', 'eval.hip', 'quantize.hip', 'deflate.hip', 'unpack.hip', 'pool.hip', 'pack.hip', 'window.hip', 'raster.hip', 'rng.hip', 'optim.hip', 'tensorstats.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-Wno-unused-result', '-Wno-unused-value',
          '-ffp-contract=fast']
 

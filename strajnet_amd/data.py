@@ -222,6 +222,64 @@ def serialize_example(features):
     return _ld(1, entries)
 
 
+def parse_example_lists(payload):
+    """tf.train.Example -> {feature name: float32 array | int64 array} for its FloatList (Feature.float_list=2) and Int64List
+    (Feature.int64_list=3) features, packed or not: what a Waymo motion record holds (strajnet_amd/raster.py,
+    tracks_from_motion_example).  BytesList features are parse_example's."""
+    out = {}
+    for fno, wt, feats in _fields(memoryview(payload)):
+        if fno != 1 or wt != 2:
+            continue
+        for f2, w2, entry in _fields(feats):
+            if f2 != 1 or w2 != 2:
+                continue
+            name, value = None, None
+            for f3, w3, v in _fields(entry):
+                if f3 == 1:
+                    name = bytes(v).decode()
+                elif f3 == 2:
+                    for f4, w4, lst in _fields(v):
+                        if f4 == 2 and w4 == 2:             # float_list: value = 1, packed (one length-delimited run) or one fixed32 each
+                            parts = [bytes(b) for f5, w5, b in _fields(lst) if f5 == 1 and w5 in (2, 5)]
+                            value = np.frombuffer(b''.join(parts), '<f4').astype(np.float32)
+                        elif f4 == 3 and w4 == 2:           # int64_list: value = 1, packed varints or one varint each
+                            ints = []
+                            for f5, w5, b in _fields(lst):
+                                if f5 != 1:
+                                    continue
+                                if w5 == 0:
+                                    ints.append(b)
+                                elif w5 == 2:
+                                    i = 0
+                                    while i < len(b):
+                                        r, i = _varint(b, i)
+                                        ints.append(r)
+                            value = np.array([r - (1 << 64) if r >> 63 else r for r in ints], np.int64)
+            if name is not None and value is not None:
+                out[name] = value
+    return out
+
+
+def serialize_example_lists(features):
+    """{name: float array | integer array | bytes} -> tf.train.Example bytes with packed FloatList / Int64List / BytesList features: the
+    writer that matches parse_example_lists (and parse_example for the bytes), for tests and synthetic motion records."""
+    entries = b''
+    for name in sorted(features):
+        v = features[name]
+        if isinstance(v, (bytes, bytearray, memoryview)):
+            feat = _ld(1, _ld(1, bytes(v)))
+        else:
+            v = np.asarray(v)
+            if v.dtype.kind == 'f':
+                feat = _ld(2, _ld(1, v.astype('<f4').tobytes()) if v.size else b'')
+            elif v.dtype.kind in 'iub':
+                feat = _ld(3, _ld(1, b''.join(_enc_varint(int(i) & ((1 << 64) - 1)) for i in v.reshape(-1))) if v.size else b'')
+            else:
+                raise ValueError(f'feature {name}: no tf.Example list for dtype {v.dtype}')
+        entries += _ld(1, _ld(1, name.encode()) + _ld(2, feat))
+    return _ld(1, entries)
+
+
 def batches(examples, batch_size):
     buf = []
     for e in examples:
